@@ -2,7 +2,15 @@
 """Benchmark of the argus training hot path on MI355X (BASELINE.json metric / configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--hw 256 256] [--dtype bf16]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, the
+result line (metric, value, unit, higher_is_better, dtype, ms_per_step and the workload's description).
+--full adds everything listed under "With --full also reported" below, each with runs of its own
+outside the timed region. --dump-outputs DIR writes what the last timed step handed its caller
+(DIR/<name>.npy, float32; see dump_outputs) so that two builds can be compared output for output: with
+the same arguments the inputs and the initial weights are the same from run to run.
 
 A step = one fused native train step (argus/train.py:298-320) on a device-resident synthetic batch:
 images (B, 6, H, W) fp32 in [0,1] (uint8-uniform pixels / 255, seed 1000+rank) and SE(3) targets
@@ -11,7 +19,7 @@ backward -> [RCCL SUM all-reduce, bucketed, overlapped] -> clip_grad_norm_(1.0) 
 Weights: seeded random init (torch.manual_seed(42)) of the reference architecture.
 value = images/s over all ranks (one sample = 2 camera images); weak scaling (B per rank fixed).
 
-Also reported:
+With --full also reported:
   roofline     - the dominant kernel instantiation (conv GEMM or BN pass; largest total time in one
                  probe step),
                  timed live over the timed region by the library's kernel timer (start/stop HIP
@@ -242,6 +250,89 @@ def launch(gpus: int, argv: list[str], script: str | None = None) -> int:
     return subprocess.call(launcher_argv(gpus, _free_port(), argv, script), env=env)
 
 
+def timed_steps(trainer, images, targets, steps: int, world: int):
+    """The timed region: ``steps`` fused train steps between two device synchronisations (and two
+    barriers when there are several ranks). Returns (seconds, the last step's per-sample losses)."""
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    losses = None
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        losses = trainer.step(images, targets)
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    return time.perf_counter() - t0, losses
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of each flat buffer (4 MiB as float32)
+
+
+def step_outputs(trainer, losses: torch.Tensor) -> dict:
+    """What the caller of FusedTrainer.step holds after a step, as float32 CPU tensors: the per-sample
+    losses it returns, the gradient norm, and the state it leaves behind - the gradients, the updated
+    parameters (a fixed, seeded sample of DUMP_SAMPLE elements of each flat buffer, in index order) and
+    the model's floating-point buffers (the BN running statistics) in named_buffers() order."""
+    flat = trainer.flat
+    if flat.total > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(20240)
+        idx = torch.randint(0, flat.total, (DUMP_SAMPLE,), generator=g).sort().values.to(flat.param.device)
+        grad, param = flat.grad[idx], flat.param[idx]
+    else:
+        grad, param = flat.grad, flat.param
+    bufs = [b.detach().flatten().float() for _, b in trainer.model.named_buffers() if b.is_floating_point()]
+    out = {"losses": losses, "grad_norm": trainer.grad_norm(), "grad_sample": grad, "param_sample": param}
+    if bufs:
+        out["running_stats"] = torch.cat(bufs)
+    return {k: v.detach().float().cpu().clone() for k, v in out.items()}
+
+
+def dump_outputs(directory: str, outputs: dict) -> None:
+    """Write each array of ``outputs`` as <directory>/<name>.npy (float32)."""
+    import numpy as np
+
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(d / f"{name}.npy", t.numpy().astype(np.float32, copy=False))
+
+
+def headline(args, world: int, B: int, H: int, W: int, elapsed: float) -> dict:
+    """The head of the result line: the throughput figure, the time of one timed step and the
+    description of the workload."""
+    images_per_s = world * B * 2 * args.steps / elapsed
+    return {
+        "metric": f"train images/sec + val SE(3) geodesic err, 2x{H}x{W} RGB",
+        "value": round(images_per_s, 2),
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "dtype_detail": ("OCP MX-fp8 (e4m3 + E8M0 scale per 32 K-elements) operands for the 3x3 conv forward "
+                         "(stride 1) and data-gradient GEMMs with >= 128 reduction channels (policy key 37); the "
+                         "stride-1 ones read MX-fp8 copies of their inputs that the BN apply passes store beside "
+                         "the bf16 tensors; bf16 tensors, BN, 1x1 convs, weight gradients and the 64-channel "
+                         "convs; fp32 accumulation, statistics, head, optimizer"
+                         if args.dtype == "fp8" else None),
+        "data": "synthetic (uint8-uniform images, Exp(N(0,0.5^2)) SE(3) targets, seeded random-init weights)",
+        "config": {
+            "workload": f"{_config_name(B, H, W, world)}: fused train step, {B} samples "
+                        f"({2 * B} images) of {H}x{W} per rank, 2 cams, ResNet-50 + MLP head, {args.dtype}",
+            "batch_per_rank": B, "global_batch": B * world, "image_hw": [H, W], "parallelism": f"dp{world}",
+            "baseline_config": _config_name(B, H, W, world).split(" ")[0],
+            "scaling_series": ("weak: the same per-rank batch at every N (the default 64 is configs[1]'s; configs[2], "
+                               "the 8-GPU B=256-per-rank line, is --batch 256)"),
+        },
+        "samples_per_s": round(images_per_s / 2, 2),
+    }
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -252,9 +343,15 @@ def main() -> None:
                          "256 = configs[2]'s per-rank batch)")
     ap.add_argument("--hw", type=int, nargs=2, default=(256, 256))
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beside the headline figure (roofline and critical-"
+                         "path kernel timers, validation against the CPU oracle, CPU baseline); the options below "
+                         "shape those legs and need --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed its caller as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--kernels", action="store_true", help="print the probe step's per-kernel table to stderr")
+    ap.add_argument("--kernels", action="store_true", help="print the probe step's per-kernel table to stderr (implies --full)")
     ap.add_argument("--no-isolated", action="store_true",
                     help="skip the two untimed no-overlap steps that measure the dominant kernel alone")
     ap.add_argument("--no-val-oracle", action="store_true", help="skip the CPU oracle validation check")
@@ -263,6 +360,9 @@ def main() -> None:
     ap.add_argument("--tune", nargs="*", default=[],
                     help="dev: kernel-selection overrides key=value (argus_conv_policy_default keys)")
     args = ap.parse_args()
+    args.full = args.full or args.kernels  # the table is of the probe steps, which only a full run takes
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if needs_launch(args.gpus, os.environ):
         sys.exit(launch(args.gpus, sys.argv[1:]))
 
@@ -298,6 +398,21 @@ def main() -> None:
 
     for _ in range(args.warmup):
         trainer.step(images, targets)
+    if not args.full:  # the plain run: the timed steps, their outputs, the headline
+        elapsed, losses = timed_steps(trainer, images, targets, args.steps, world)
+        el = torch.tensor([elapsed], device=dev)
+        if world > 1:
+            dist.all_reduce(el, op=dist.ReduceOp.MAX)
+        if rank == 0:
+            out = headline(args, world, B, H, W, el.item())
+            out["train_loss"] = round(losses.mean().item(), 6)
+            out["max_memory_allocated_gb"] = round(torch.cuda.max_memory_allocated(dev) / 2**30, 3)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, step_outputs(trainer, losses))
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # find the dominant kernel instantiation (largest total time) over three instrumented steps (the
     # two 128x128 weight-gradient instantiations are within ~10 % of each other: one step's noise
     # could pick either)
@@ -327,19 +442,13 @@ def main() -> None:
     timer = KernelTimer(dom)  # exact-name prefix: only this instantiation is timed
 
     torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
     if trainer.distributed:
         trainer.tail_events = []
     timer.start()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        losses = trainer.step(images, targets)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed, losses = timed_steps(trainer, images, targets, args.steps, world)
     timer.stop()
+    if rank == 0 and args.dump_outputs:  # before the untimed steps below change them
+        dump_outputs(args.dump_outputs, step_outputs(trainer, losses))
     tail_ms = None
     if trainer.tail_events:
         tail_ms = sum(a.elapsed_time(b) for a, b in trainer.tail_events) / len(trainer.tail_events)
@@ -458,36 +567,10 @@ def main() -> None:
                 "peak": peak_flops if mf else HBM_PEAK_GBS, "unit": "TFLOP/s" if mf else "GB/s",
                 "frac": round(tf / peak_flops if mf else gb / HBM_PEAK_GBS, 4),
                 "achieved_tflops": round(tf, 2), "achieved_gbs": round(gb, 1)}
-    images_per_s = world * B * 2 * args.steps / elapsed
     # algorithmic conv FLOPs per step: fwd + dgrad + wgrad (the stem has no dgrad)
     step_flops = sum((2 if n == "resnet.conv1" else 3) * c.flops for n, c in eng.convs.items())
     out = {
-        "metric": f"train images/sec + val SE(3) geodesic err, 2x{H}x{W} RGB",
-        "value": round(images_per_s, 2),
-        "unit": "images/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "dtype_detail": ("OCP MX-fp8 (e4m3 + E8M0 scale per 32 K-elements) operands for the 3x3 conv forward "
-                         "(stride 1) and data-gradient GEMMs with >= 128 reduction channels (policy key 37); the "
-                         "stride-1 ones read MX-fp8 copies of their inputs that the BN apply passes store beside "
-                         "the bf16 tensors; bf16 tensors, BN, 1x1 convs, weight gradients and the 64-channel "
-                         "convs; fp32 accumulation, statistics, head, optimizer"
-                         if args.dtype == "fp8" else None),
-        "data": "synthetic (uint8-uniform images, Exp(N(0,0.5^2)) SE(3) targets, seeded random-init weights)",
-        "config": {
-            "workload": f"{_config_name(B, H, W, world)}: fused train step, {B} samples "
-                        f"({2 * B} images) of {H}x{W} per rank, 2 cams, ResNet-50 + MLP head, {args.dtype}",
-            "batch_per_rank": B, "global_batch": B * world, "image_hw": [H, W], "parallelism": f"dp{world}",
-            "baseline_config": _config_name(B, H, W, world).split(" ")[0],
-            "scaling_series": ("weak: the same per-rank batch at every N (the default 64 is configs[1]'s; configs[2], "
-                               "the 8-GPU B=256-per-rank line, is --batch 256)"),
-        },
+        **headline(args, world, B, H, W, elapsed),
         "rccl_world_size": dist.get_world_size() if world > 1 else 1,
         "collective_backend": (dist.get_backend() if world > 1 else None),
         "allreduce_tail_ms_per_step": round(tail_ms, 4) if tail_ms is not None else None,
@@ -525,7 +608,6 @@ def main() -> None:
             "mfma_counters": pmc_mfma(crit, B, H, W, args.dtype),
             "main_stream_busy_ms_per_step": round(main_busy_ms, 3),
         },
-        "samples_per_s": round(images_per_s / 2, 2),
         "step_conv_tflops_per_gpu": round(step_flops / (ms * 1e-3) / 1e12, 2),
         "step_conv_frac_of_bf16_peak": round(step_flops / (ms * 1e-3) / 1e12 / BF16_DENSE_PEAK_TFLOPS, 4),
         "train_loss": round(train_loss, 6),

@@ -27,8 +27,8 @@ if [ "$PART" = a ]; then
   cp gpurun_out/pmc_$TAG/summary.txt $O/pmc_mfma_summary.txt
   cp $O/pmc_traffic.json profiles/${TAG}_pmc_traffic.json
   cp $O/pmc_mfma_summary.json profiles/${TAG}_pmc_mfma_summary.json
-  timeout -k 10 240 python3 -u bench.py > $O/bench.json 2> $O/bench.err
-  timeout -k 10 180 python3 -u bench.py --batch 256 --no-cpu-baseline > $O/bench_b256.json 2> $O/bench_b256.err
+  timeout -k 10 240 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err
+  timeout -k 10 180 python3 -u bench.py --full --batch 256 --no-cpu-baseline > $O/bench_b256.json 2> $O/bench_b256.err
 elif [ "$PART" = c ]; then
   # configs[4]'s per-rank batch (B=512): PMC traffic and MFMA counters for fp8 and bf16, then the lines
   for DT in fp8 bf16; do
@@ -44,9 +44,9 @@ elif [ "$PART" = c ]; then
     # keep the merge-back small: the B=512 traces and counter dumps are summarised above
     find gpurun_out/prof_${TAG}_b512_$DT gpurun_out/pmc_${TAG}_b512_$DT -name "*.csv" -size +2M -delete
   done
-  timeout -k 10 240 python3 -u bench.py --dtype fp8 --batch 512 --no-cpu-baseline --steps 5 --warmup 2 \
+  timeout -k 10 240 python3 -u bench.py --full --dtype fp8 --batch 512 --no-cpu-baseline --steps 5 --warmup 2 \
     > $O/bench_b512_fp8.json 2> $O/bench_b512_fp8.err
-  timeout -k 10 240 python3 -u bench.py --batch 512 --no-cpu-baseline --steps 5 --warmup 2 \
+  timeout -k 10 240 python3 -u bench.py --full --batch 512 --no-cpu-baseline --steps 5 --warmup 2 \
     > $O/bench_b512_bf16.json 2> $O/bench_b512_bf16.err
 else
   bash tools/profile_round.sh ${TAG}_376 --hw 376 672 --batch 128 --steps 5 --warmup 2
@@ -56,7 +56,7 @@ else
   cp gpurun_out/pmc_${TAG}_376/summary.txt $O/376x672_pmc_mfma_summary.txt
   cp $O/pmc_traffic_376x672.json profiles/${TAG}_376x672_pmc_traffic.json
   cp $O/376x672_pmc_mfma_summary.json profiles/${TAG}_376x672_pmc_mfma_summary.json
-  timeout -k 10 240 python3 -u bench.py --hw 376 672 --batch 128 --no-cpu-baseline --kernels \
+  timeout -k 10 240 python3 -u bench.py --full --hw 376 672 --batch 128 --no-cpu-baseline --kernels \
     > $O/bench_376x672.json 2> $O/bench_376x672_kernels.txt
 fi
 echo "measure $PART done"

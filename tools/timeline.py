@@ -3,7 +3,7 @@
     python tools/timeline.py OUT/run_kernel_trace.csv [--steps K]
 
 Steps are delimited by the optimizer kernel (adam_kernel): one step = from the end of one Adam to the
-end of the next. Trace a bench run with --no-isolated (tools/prof_timeline.sh does): otherwise the
+end of the next. Trace a bench run with --full --no-isolated (tools/prof_timeline.sh does): otherwise the
 last steps are bench.py's two untimed no-overlap steps. For the last K steps it reports the step wall time, each HIP stream's busy time
 (union of its kernel intervals) and idle gaps, and the main stream's (the one running Adam) busy time
 per kernel family — i.e. what the critical path is made of and how much the side stream overlaps.
@@ -59,7 +59,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--first", type=int, default=None,
                     help="index (0-based, in Adam launches) of the first step to report; default: the last --steps "
-                         "steps. bench.py runs warmup + 2 x 3 probe steps before its timed region and 5 critical-path "
+                         "steps. bench.py --full runs warmup + 2 x 3 probe steps before its timed region and 5 critical-path "
                          "timer steps after it, whose per-launch events perturb the main stream")
     ap.add_argument("--list", action="store_true", help="also list the last step's main-stream kernels in order "
                                                         "(start offset, gap before, duration)")
