@@ -1334,13 +1334,6 @@ static const Policy kDefaultPolicy = [] {
   //     B=64 13.65 vs 13.68-13.72 ms, B=256 46.21 vs 47.03-47.13 ms, 376x672 B=128 90.23 vs 90.71-91.56 ms;
   //     8 level, 2 slower (14.6 ms at B=64): profiles/r06a_ab_keys.txt, r06b_ab_*_key49*.txt
   p.v[kDgradApMaxCols] = 4;
-  // 50: the LDS-DMA weight gradients sum their split partials inside the launch (reducing workgroups
-  //     after the compute grid, conv_wgdma.hip) instead of a wgrad_reduce launch; the caller's workspace
-  //     must end in kWgFoldCtrBytes of zeros (argus_conv_wgrad_workspace_bytes includes them). Engine
-  //     A/B at B=64: 14.50 vs 13.78-13.85 ms (profiles/r06a_ab_keys.txt): the reducing workgroups wait
-  //     for their tile's last split while holding a CU's LDS, and the write-through partials leave L2:
-  //     off (dW bit-identical either way)
-  p.v[kWgradFold] = 0;
   // 51: the 3x3 halo forward / data gradient (128-column tiles) with a four-stage weight ring on
   //     384-position halo images where the tile's halo fits (the 32- and 16-wide layers at 256 x 256):
   //     alone (tools/dgradbench.py --convs conv2, B=64) layer 2 51.5 / 68.5 vs 51.6 / 68.9 us (plain /
@@ -1930,8 +1923,7 @@ size_t conv_wgrad_ws(const argus_conv_desc& d, int dtype) {
     const size_t hb = (size_t)hs * d.k * 9 * d.c * sizeof(float);
     b = hb > b ? hb : b;
   }
-  // + the folded reduction's counters (key 50): the last kWgFoldCtrBytes, past every kernel's partials
-  return b + kWgFoldCtrBytes;
+  return b;
 }
 
 template <typename T, int BM, int BN, bool STEM, bool PRO, bool FAST, bool AP>
@@ -2016,20 +2008,8 @@ static int conv_wgrad_impl(const argus_conv_desc& d, int dtype, const void* x, c
   if (d.stem && pol[kStemLdsWgrad] && stem_wgrad_launch(d, dtype, x, dy, ap, ws, ws_bytes, &splits, st)) {
     if (int e = check_launch("stem_wgrad_kernel")) return e;
   } else if (!sc && wgrad_dma_ok(d, dtype, pl.bm, pl.bn, pol[kWgradDma], ap != nullptr, pol[kWgradDmaGather])) {
-    // key 50: the split sum folded into the launch (its last kWgFoldCtrBytes of ws hold the counters,
-    // zero before the first launch; every launch leaves them zero)
-    const int ft = wgrad_dma_fold_tiles(d, pol[kWgradDma], pol[kWgradDmaGather], ap != nullptr);
-    const size_t need = (size_t)pl.splits * d.k * pl.N * sizeof(float);
-    const bool fold = pol[kWgradFold] && ft > 0 && (2 * ft + 1) * 4 <= (int)kWgFoldCtrBytes &&
-                      ws_bytes >= need + kWgFoldCtrBytes;
-    if (fold) {
-      p.fold.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + ((ws_bytes - kWgFoldCtrBytes) & ~(size_t)255));
-      p.fold.dw = dw;
-      p.fold.sl = wgrad_reduce_lanes(d.k, pl.N);
-    }
     wgrad_dma_launch(d, p, pol[kWgradDma], pol[kWgradDmaGather], pl.splits, pol[kWgradDmaStages], st);  // LDS-DMA ring
     if (int e = check_launch("wgrad_dma_kernel")) return e;
-    if (fold) return ARGUS_OK;
   } else if (ap) {  // the register-staged kernel stages the apply; no halo / glds variant does
     if (dtype == ARGUS_BF16) dispatch_wg<bf16>(p, pl, st);
     else dispatch_wg<float>(p, pl, st);

@@ -22,14 +22,12 @@ Eval mode uses running statistics (bn_eval_coeffs) and skips all statistics / ru
 from __future__ import annotations
 
 import ctypes as C
-import collections
 import contextlib
 from dataclasses import dataclass
 
 import torch
 
-from argus_amd._lib import (BnFwdFin, BF16, F32, FP8, BnBwdEpilogue, BnBwdPrologue, ConvDesc, DeviceEvent, lib, ptr,
-                             stream)
+from argus_amd._lib import BnFwdFin, BF16, F32, FP8, BnBwdEpilogue, BnBwdPrologue, ConvDesc, lib, ptr, stream
 
 
 @dataclass(frozen=True)
@@ -135,15 +133,6 @@ class ResNetEngine:
         # ring buffers it reuses was measured too (-2.5 %: it waits earlier than the per-buffer guards).
         # False issues every weight gradient as soon as its dy is ready.
         self.side_batch = True
-        # a block's deferred weight gradients issued in reverse order (conv1 first; they write separate
-        # dW buffers and share one workspace in stream order, so the results are identical)
-        self.side_reverse = False
-        # cross-stream events with a device-scope release / acquire (argus_event_*, hipEventDisableSystemFence)
-        # instead of torch.cuda.Event; the collectives' stream hand-off (_comm) keeps torch's events either
-        # way. Off: measured 13.34-13.43 vs 13.28-13.34 ms at B=64 (profiles/r06j_ab_b64_light_events.txt);
-        # the ~6 us main-stream gap at each cross-stream event is not the system-scope fence
-        self.light_events = False
-        self._ev_keep: collections.deque = collections.deque(maxlen=512)  # recent events, destroyed late
         self._deferred: list = []  # (cv, fn, buffer data_ptrs)
         self._side_seq = 0
         self._waited_seq = 0
@@ -165,14 +154,6 @@ class ResNetEngine:
         # (argus_conv_dgrad_wgrad_bn) instead of the dgrad + the side stream's wgrad_apply, which read
         # both 256-channel tensors again; set before the first forward
         self.fuse_dgw = True
-        # the 3x3 data gradients (compute-bound: ~500 FLOP/B) run alone: before each one the main stream
-        # waits for the weight gradients already issued on the side stream, whose workgroups would
-        # otherwise hold the CUs' LDS and registers beside it (the block's own deferred weight gradients
-        # are issued after it, at the block's end, as usual)
-        self.gate3x3 = False
-        # ... only for the blocks of at most this width (64: layer 1, whose halo data gradients run at 76 KB of
-        # LDS a workgroup and lose CUs to the side stream's 128-148 KB weight-gradient workgroups); 0 = off
-        self.gate3x3_width = 0
         # the bottleneck tail on the bf16 schedule: conv3's forward only reduces bn3's statistics (nothing
         # stored), then one pass recomputes its C tile and applies bn3 + the residual + ReLU there
         # (argus_conv_fwd_bn_out): the bn_apply pass no longer reads y3 back (bit-identical outputs)
@@ -348,8 +329,7 @@ class ResNetEngine:
         self.bwd_part = self._f(max_bwd * 2)
         self.bwd_part2 = self._f(max_bwd * 2)  # second branch (downsample BN) of a dual reduce
         ws = max(L.dll.argus_conv_wgrad_workspace_bytes(C.byref(cv.desc), dt) for cv in convs.values())
-        # zeroed: a folded DMA weight gradient (policy key 50) keeps its counters in the last bytes
-        self.wg_ws = torch.zeros(ws, dtype=torch.uint8, device=self.device)
+        self.wg_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
         self.wg_ws_bytes = ws
         wss = L.dll.argus_conv_wgrad_workspace_bytes(C.byref(convs["resnet.conv1"].desc), dt)
         # the stem weight gradient's workspace; also the first block's downsample weight gradient's, which
@@ -357,7 +337,7 @@ class ResNetEngine:
         ds0 = self.blocks[0].prefix + ".downsample.0"
         if ds0 in convs:
             wss = max(wss, L.dll.argus_conv_wgrad_workspace_bytes(C.byref(convs[ds0].desc), dt))
-        self.wg_ws_stem = torch.zeros(wss, dtype=torch.uint8, device=self.device)
+        self.wg_ws_stem = torch.empty(wss, dtype=torch.uint8, device=self.device)
         self.stages_pro = {n: bool(L.dll.argus_conv_dgrad_stages_prologue(C.byref(cv.desc), self.cdt))
                            for n, cv in convs.items() if not cv.desc.stem}
         self.gbuf = [self._t(max_elems) for _ in range(3)]  # avgpool dh; dza / dzb (the dz of bn2 / bn1)
@@ -737,8 +717,6 @@ class ResNetEngine:
             # conv2 -> bn1 (dm1 goes to a ring buffer when the side stream's conv1 wgrad reads it)
             if wg1_apply:
                 dzb = self._next_dy()
-            if self.gate3x3 or b.width <= self.gate3x3_width:
-                self._drain_side()
             r1 = self._dgrad_bn(pf + ".conv2", dza if pro2 else dy2, dzb, None, pf + ".bn1", a["y1"], 2, P=P, G=G,
                                 pro=pro2, x8=self.x8buf if x8d else None)
             cap("b_dy2", dy2, px_o * b.width, (N, ho, wo, b.width))
@@ -1031,7 +1009,7 @@ class ResNetEngine:
         items, self._deferred = self._deferred, []
 
         def run():
-            for cv, fn, _ in (items[::-1] if self.side_reverse else items):
+            for cv, fn, _ in items:
                 self._launch(cv, 2, fn)
 
         done = self._on_side(run)
@@ -1040,11 +1018,10 @@ class ResNetEngine:
             self._pending[bp] = (self._side_seq, done)
         self._last_side = done
 
-    def _event(self):
-        """A cross-stream event (record(stream) / wait(stream)): device-scope (light_events) or torch's."""
-        ev = DeviceEvent() if self.light_events else torch.cuda.Event()
-        self._ev_keep.append(ev)
-        return ev
+    @staticmethod
+    def _event():
+        """A cross-stream event (record(stream) / wait(stream))."""
+        return torch.cuda.Event()
 
     def _on_side(self, fn):
         """Run ``fn``'s launches on the side stream after the main stream's work so far; returns the
@@ -1092,14 +1069,6 @@ class ResNetEngine:
         self._side.wait_event(ev)
         with torch.cuda.stream(self._side):
             yield
-
-    def _drain_side(self) -> None:
-        """Main stream waits for the weight gradients issued on the side stream so far (the deferred ones
-        stay deferred): nothing of the side stream is resident during the next main-stream launch."""
-        if self._last_side is not None and self._waited_seq < self._side_seq:
-            self._last_side.wait(torch.cuda.current_stream())
-            self._pending.clear()
-            self._waited_seq = self._side_seq
 
     def _join(self) -> None:
         """Main stream waits for every weight gradient issued so far."""

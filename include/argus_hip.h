@@ -276,7 +276,13 @@ int argus_conv_dgrad_bn_x8(const argus_conv_desc* d, const void* dy8, const void
  * weight gradients on the LDS-DMA ring kernel with 128 x 128 tiles (1), 128 x 256 tiles where
  * Cin % 256 == 0 for the BN-backward-apply form (2) or both forms (3), or the register-staged one (0);
  * key 46 the pixel count up to which 1x1 weight gradients take half the split target (key 6); key 47
- * the stride-2 plain bf16 weight gradients (1x1, 3x3) on the DMA kernel with gathered x rows (1) or not (0).
+ * the stride-2 plain bf16 weight gradients (1x1, 3x3) on the DMA kernel with gathered x rows: 0 never,
+ * 1 at every size, a larger value up to that many output pixels (default 131072); key 48 the LDS ring
+ * stages (2..5, default 4) of the 128 x 256 BN-backward-apply form of that kernel; key 49 the most
+ * 128-column tiles for which a 1x1 data gradient stages its apply prologue itself (more: dy is
+ * materialised first; 0 = always staged; default 4); key 51 the 3x3 halo forward / data gradient with a
+ * four-stage weight ring where the tile's halo fits 384 positions (1) or the three-stage ring (0,
+ * default). Key 50 was removed and is unknown, like key 30.
  * (Keys scaled with the batch keep a smaller batch's kernel selection that of the larger one:
  * tests/test_gpu_parity.py stage-checks the benched configurations' kernels that way.) */
 int argus_conv_policy_default(int key);
@@ -332,19 +338,6 @@ int argus_ktimer_disable(void);
 int argus_ktimer_count(void);
 int argus_ktimer_get(int index, char* name, int name_len, int64_t* launches, double* total_ms,
                      double* work, double* bytes);
-
-/* ---- cross-stream ordering (ABI 19) ------------------------------------------------------------
- * Events for ordering two streams of one device: created with hipEventDisableTiming |
- * hipEventDisableSystemFence, so recording one performs a device-scope release and waiting on it a
- * device-scope acquire, without the system-scope cache writeback / invalidation a default event carries.
- * Work on this device only (the weight-gradient side stream and the main stream of one process); the
- * host and other devices need a default event. Replaces the torch.cuda.Event record / wait_event pairs
- * the DDP-free training step of argus/train.py:298-321 would use between two streams (it uses one). */
-typedef void* argus_event_t; /* hipEvent_t */
-int argus_event_create(argus_event_t* event);
-int argus_event_record(argus_event_t event, argus_stream_t stream);
-int argus_stream_wait_event(argus_stream_t stream, argus_event_t event);
-int argus_event_destroy(argus_event_t event);
 
 /* ---- BatchNorm2d (train: batch stats, eps, momentum; eval: running stats) --------------------- */
 /* Workspace of argus_bn_finalize / argus_bn_bwd_finalize / the folded finalize of argus_conv_dgrad_bn

@@ -75,6 +75,8 @@ def main():
     m = NCameraCNN(compute_dtype=a.dtype, kernel_tuning=tune or None).to(dev).train()
     eng = m._engine(dev)
     for k, v in attrs.items():
+        if not hasattr(eng, k):  # e.g. a retired switch: never measure the defaults under its name
+            raise SystemExit(f"the engine has no attribute {k!r}")
         cur = getattr(eng, k)
         setattr(eng, k, v == "1" if isinstance(cur, bool) else type(cur)(int(v)))
     tr = FusedTrainer(m, lr=1e-4, max_grad_norm=1.0)
