@@ -18,7 +18,7 @@ CSRC = HERE / "csrc"
 OUT = HERE / "libargus_hip.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-SOURCES = ["capi.cpp", "ktimer.cpp", "conv.hip", "conv_glds.hip", "conv_halo.hip", "conv_dgw.hip", "conv_p1x1.hip", "conv_wgdma.hip", "reduce.hip", "stem.hip", "bn.hip", "head.hip", "loss.hip", "optim.hip", "augment.hip"]
+SOURCES = ["capi.cpp", "ktimer.cpp", "conv.hip", "conv_x3.hip", "conv_glds.hip", "conv_halo.hip", "conv_dgw.hip", "conv_p1x1.hip", "conv_wgdma.hip", "reduce.hip", "stem.hip", "bn.hip", "head.hip", "loss.hip", "optim.hip", "augment.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 
@@ -28,6 +28,8 @@ def _compile(src: str, verbose: bool) -> Path:
     obj.parent.mkdir(exist_ok=True)
     srcp = CSRC / src
     deps = [srcp, *CSRC.glob("*.h"), HERE.parent / "include" / "argus_hip.h"]
+    if src == "conv_x3.hip":  # it includes conv.hip (the bf16x3 instantiations of its kernels)
+        deps.append(CSRC / "conv.hip")
     if obj.exists() and obj.stat().st_mtime > max(d.stat().st_mtime for d in deps):
         return obj
     cmd = [HIPCC, *FLAGS, "-c", str(srcp), "-o", str(obj)]

@@ -27,7 +27,7 @@ using namespace argus;
 
 extern "C" {
 
-int argus_abi_version(void) { return 20; }
+int argus_abi_version(void) { return 21; }
 
 const char* argus_last_error(void) { return g_last_error.c_str(); }
 

@@ -13,7 +13,9 @@
 //                  ds_read_b64_tr_b16 (bf16) — fp32 partial slabs, then a deterministic reduce.
 //
 // Tiles: 256 threads = 4 waves (2 x 2), wave tile (BM/2) x (BN/2) of 16x16 MFMA blocks.
-// bf16: v_mfma_f32_16x16x32_bf16, K-step 64; fp32 (parity path): v_mfma_f32_16x16x4_f32, K-step 32.
+// bf16: v_mfma_f32_16x16x32_bf16, K-step 64; fp32 (parity path): v_mfma_f32_16x16x4_f32, K-step 32;
+// fp32 tensors with bf16x3 split operands (element tag f32x3, policy key 53; igemm.h): three
+// v_mfma_f32_16x16x32_bf16 per K-step of 32, instantiated in conv_x3.hip.
 // LDS rows are 8 x 16-byte chunks, XOR-swizzled (chunk ^ ((row>>1)&7)) so the ds_read_b128
 // fragment reads are bank-conflict free. Register-staged double buffering: the global loads of
 // k-step t+1 are issued before the MFMAs of step t and written to the other LDS buffer after.
@@ -80,8 +82,10 @@ template <typename T, int BN> constexpr int epi_ld() { return BN + 16 / (int)siz
 // OCC = workgroups per CU the kernel is built for: 2 -> double-buffered LDS + 2-deep register
 // prefetch ring (deep-K GEMMs); 3 or 4 -> one LDS buffer, no ring, <= 168 / 128 VGPRs (K <= 2
 // k-steps: the 1x1 convs whose time is load/epilogue latency, hidden by more resident workgroups).
-template <typename T, int BM, int BN, bool STEM, bool PRO, int OCC, int BWX>
+template <typename TT, int BM, int BN, bool STEM, bool PRO, int OCC, int BWX>
 __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
+  using T = typename Elem<TT>::type;            // storage type of the tensors
+  constexpr bool X3 = Elem<TT>::X3;             // fp32 tensors, bf16x3 split operands (igemm.h)
   constexpr int BW = BWX & 7;                   // BN-backward epilogue variant
   constexpr bool AP = (BWX & kApplyBit) != 0;   // BN-backward apply prologue
   constexpr bool F8 = (BWX & kFp8Bit) != 0;     // MX-fp8 operands (bf16 activations, fp8 weights)
@@ -90,6 +94,7 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
   constexpr bool YREC = (BWX & kYrecBit) != 0;  // BN-backward epilogue: y recomputed (BnBwdEpi::yx)
   static_assert(!YREC || ((BW == 3 || BW == 4) && !F8 && !STEM && !PRO && sizeof(T) == 2), "y recompute: bf16 dgrad");
   static_assert(!F8 || (sizeof(T) == 2 && !STEM && !PRO), "fp8: bf16 tensors, no BN+ReLU prologue");
+  static_assert(!X3 || (!OUT && !YREC && !F8), "bf16x3: the fp32 forward / dgrad variants");
   constexpr int E = Chunk<T>::E;
   constexpr int EF = F8 ? 2 * E : E;  // elements one thread stages per row per k-step
   constexpr int BKE = 8 * EF;  // K elements per k-step (8 chunks of 16 B per LDS row)
@@ -317,6 +322,22 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
       }
       return;
     }
+    if constexpr (X3) {
+      // a 128-byte row holds its 32 k-elements as bf16 hi parts (bytes 0-63: chunks 0-3) and lo parts
+      // (bytes 64-127: chunks 4-7); this thread's 4 elements are 8 bytes of each, chunks XOR-swizzled
+      uint2* L2 = reinterpret_cast<uint2*>(L);
+      auto put = [&](int row8, int row, u32x4 v) {  // row8: the row's first chunk
+        uint2 hi, lo;
+        split_x3(v, hi, lo);
+        L2[(row8 + ((cidx >> 1) ^ swz8(row))) * 2 + (cidx & 1)] = hi;
+        L2[(row8 + ((4 + (cidx >> 1)) ^ swz8(row))) * 2 + (cidx & 1)] = lo;
+      };
+#pragma unroll
+      for (int i = 0; i < AR; ++i) put(((tid >> 3) + 32 * i) * 8, (tid >> 3) + 32 * i, S.a[i]);
+#pragma unroll
+      for (int i = 0; i < BR; ++i) put((BM + (tid >> 3) + 32 * i) * 8, (tid >> 3) + 32 * i, S.b[i]);
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
       const int row = (tid >> 3) + 32 * i;
@@ -353,6 +374,53 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
         for (int ni = 0; ni < NI; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa, fb[ni], acc[mi][ni], 0, 0, 0, sa, 0,
                                                                           sb[ni]);
+      }
+      return;
+    }
+    if constexpr (X3) {
+      // lane group g holds k = 8g..8g+7 of both operands: the hi parts in chunk g, the lo parts in chunk
+      // g + 4 (the fp8 path's conflict-free read pattern). Per accumulator: hi*hi, hi*lo, lo*hi.
+      // 128-row tiles (MI = 4) take lo*hi in a second pass over B's hi parts, so only one half of the A
+      // fragments is live at a time: the register budget of the exact kernel's fragments. The scheduling
+      // barriers keep the compiler from hoisting the second pass's LDS reads above the first (which spilled)
+      constexpr bool TWO = MI > 2;
+      u32x4 ah[MI], al[MI];
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) {
+        const int row = wm * (BM / 2) + mi * 16 + i16;
+        ah[mi] = L[row * 8 + (g ^ swz8(row))];
+        if constexpr (!TWO) al[mi] = L[row * 8 + ((g + 4) ^ swz8(row))];
+      }
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) {
+        const int row = wn * (BN / 2) + ni * 16 + i16;
+        const u32x4 bh = L[BM * 8 + row * 8 + (g ^ swz8(row))];
+        const u32x4 bl = L[BM * 8 + row * 8 + ((g + 4) ^ swz8(row))];
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) Mma<bf16>::run(acc[mi][ni], ah[mi], bh);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) Mma<bf16>::run(acc[mi][ni], ah[mi], bl);
+        if constexpr (!TWO) {
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) Mma<bf16>::run(acc[mi][ni], al[mi], bh);
+        } else if (ni & 1) {
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if constexpr (TWO) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+          const int row = wm * (BM / 2) + mi * 16 + i16;
+          al[mi] = L[row * 8 + ((g + 4) ^ swz8(row))];
+        }
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+          const int row = wn * (BN / 2) + ni * 16 + i16;
+          const u32x4 bh = L[BM * 8 + row * 8 + (g ^ swz8(row))];
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) Mma<bf16>::run(acc[mi][ni], al[mi], bh);
+        }
       }
       return;
     }
@@ -662,15 +730,19 @@ ARGUS_DEV int swz32(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
 #ifndef ARGUS_WGRAD_OCC
 #define ARGUS_WGRAD_OCC 3
 #endif
-template <typename T, int BM, int BN, bool STEM, bool PRO, bool FAST, bool AP = false>
+template <typename TT, int BM, int BN, bool STEM, bool PRO, bool FAST, bool AP = false>
 __global__ __launch_bounds__(256, ARGUS_WGRAD_OCC) void wgrad_kernel(const WgParams p) {
+  using T = typename Elem<TT>::type;              // storage type of the tensors
+  // bf16x3 (igemm.h): fp32 rows are split while staged into a hi and a lo bf16 plane per operand, each
+  // laid out as the bf16 image (256-byte pixel rows, 32-byte slots XOR swz32), read transposed like it
+  constexpr bool X3 = Elem<TT>::X3;
   constexpr int E = Chunk<T>::E;
   constexpr bool BF = (E == 8);
   constexpr int BKP = BF ? 64 : 32;               // pixels per k-step
   constexpr int CA = BM * (int)sizeof(T) / 16;    // chunks per A row
   constexpr int CB = BN * (int)sizeof(T) / 16;
-  constexpr int RSA = BF ? 16 : CA;               // LDS row stride (chunks)
-  constexpr int RSB = BF ? 16 : CB;
+  constexpr int RSA = BF ? 16 : (X3 ? 32 : CA);   // LDS row stride (chunks); bf16x3: the two planes' rows
+  constexpr int RSB = BF ? 16 : (X3 ? 32 : CB);
   constexpr int RPA = 256 / CA, RPB = 256 / CB;   // rows per staging pass
   constexpr int PA = BKP / RPA, PB = BKP / RPB;   // passes
   constexpr int MI = BM / 32, NI = BN / 32;
@@ -794,6 +866,16 @@ __global__ __launch_bounds__(256, ARGUS_WGRAD_OCC) void wgrad_kernel(const WgPar
       }
     }
   };
+  // bf16x3: the thread's 4 fp32 of pixel `row` (channel chunk c4 of operand op: 0 = A, 1 = B) as 8 bytes
+  // in the operand's hi plane and 8 in its lo plane (BKP rows of 256 bytes each)
+  auto put_x3 = [&](int buf, int op, int row, int c4, u32x4 v) {
+    uint2 hi, lo;
+    split_x3(v, hi, lo);
+    char* at = reinterpret_cast<char*>(&lds[buf][0]) + (2 * op * BKP + row) * 256 + (((c4 >> 2) ^ swz32(row)) << 5) +
+               (c4 & 3) * 8;
+    *reinterpret_cast<uint2*>(at) = hi;
+    *reinterpret_cast<uint2*>(at + BKP * 256) = lo;
+  };
   auto store = [&](int buf, const Stage& S) {
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
@@ -809,7 +891,8 @@ __global__ __launch_bounds__(256, ARGUS_WGRAD_OCC) void wgrad_kernel(const WgPar
         for (int j = 0; j < E; ++j) d[j] = fmaf(apa[j], d[j], fmaf(apb[j], yv[j], apc[j]));
         v = pack(d);
       }
-      lds[buf][row * RSA + c] = sel(S.oka[i], v);
+      if constexpr (X3) put_x3(buf, 0, row, ca, sel(S.oka[i], v));
+      else lds[buf][row * RSA + c] = sel(S.oka[i], v);
     }
 #pragma unroll
     for (int i = 0; i < PB; ++i) {
@@ -818,13 +901,50 @@ __global__ __launch_bounds__(256, ARGUS_WGRAD_OCC) void wgrad_kernel(const WgPar
       if constexpr (BF) c = (((cb >> 1) ^ swz32(row)) << 1) | (cb & 1);
       u32x4 v = S.b[i];
       if constexpr (PRO && !STEM) v = pc.apply(v);
-      lds[buf][BKP * RSA + row * RSB + c] = sel(S.okb[i], v);
+      if constexpr (X3) put_x3(buf, 1, row, cb, sel(S.okb[i], v));
+      else lds[buf][BKP * RSA + row * RSB + c] = sel(S.okb[i], v);
     }
   };
 
   const int g = lane >> 4, i16 = lane & 15;
   auto compute = [&](int buf) {
-    if constexpr (BF) {
+    if constexpr (X3) {
+      // one K = 32 block per k-step: the bf16 branch's transposed fragment reads (rows 8g + 4h + q) on
+      // plane pl = 2 * operand + (0 hi | 1 lo); per accumulator hi*hi, hi*lo, lo*hi
+      const char* base = reinterpret_cast<const char*>(&lds[buf][0]);
+      const int q = i16 >> 2, pq = i16 & 3;
+      auto frag = [&](int pl, int slot) {
+        unsigned w[4];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int row = 8 * g + 4 * h + q;
+          const char* addr = base + (pl * BKP + row) * 256 + ((slot ^ swz32(row)) << 5) + pq * 8;
+          const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (s16x4 __attribute__((address_space(3)))*)(uintptr_t)(uint32_t)(uintptr_t)addr);
+          const uint2 u = __builtin_bit_cast(uint2, t);
+          w[2 * h] = u.x; w[2 * h + 1] = u.y;
+        }
+        return u32x4{w[0], w[1], w[2], w[3]};
+      };
+      u32x4 ah[MI], al[MI];
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) {
+        const int slot = (wm * (BM / 2) + mi * 16) >> 4;
+        ah[mi] = frag(0, slot);
+        al[mi] = frag(1, slot);
+      }
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) {
+        const int slot = (wn * (BN / 2) + ni * 16) >> 4;
+        const u32x4 bh = frag(2, slot), bl = frag(3, slot);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) Mma<bf16>::run(acc[mi][ni], ah[mi], bh);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) Mma<bf16>::run(acc[mi][ni], ah[mi], bl);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) Mma<bf16>::run(acc[mi][ni], al[mi], bh);
+      }
+    } else if constexpr (BF) {
       const char* base = reinterpret_cast<const char*>(&lds[buf][0]);
       const int q = i16 >> 2, pq = i16 & 3;
 #pragma unroll
@@ -937,6 +1057,153 @@ __global__ __launch_bounds__(256, ARGUS_WGRAD_OCC) void wgrad_kernel(const WgPar
       }
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// kernel launchers (instantiate the kernels above)
+// ------------------------------------------------------------------------------------------------
+template <typename T> static const char* elem_name() { return Elem<T>::X3 ? "argus::f32x3" : type_name<T>(); }
+
+template <typename T, int BM, int BN, bool STEM, bool PRO, int OCC, int BW>
+static const char* ig_name() {
+  static const std::string s = std::string("argus::igemm_kernel<") + elem_name<T>() + ", " + std::to_string(BM) +
+                               ", " + std::to_string(BN) + ", " + bool_name(STEM) + ", " + bool_name(PRO) + ", " +
+                               std::to_string(OCC) + ", " + std::to_string(BW) + ">";
+  return s.c_str();
+}
+
+template <typename T, int BM, int BN, bool STEM, bool PRO, int OCC, int BW = 0>
+static void launch_ig(const IgParams& p0, int maxM, hipStream_t st) {
+  IgParams p = p0;
+  plan_fin(p, BM);
+  plan_ffin(p, BM);
+  const int ntiles = p.N / BN;
+  dim3 grid(cdiv(maxM, BM) * ntiles, 1, p.nphase);
+  timed_launch(ig_name<T, BM, BN, STEM, PRO, OCC, BW>(), igemm_kernel<T, BM, BN, STEM, PRO, OCC, BW>, grid,
+               dim3(256), st, p);
+}
+
+template <typename T, bool PRO, int OCC, int BW = 0>
+static void dispatch_ig(const IgParams& p, int maxM, int bm, int bn, hipStream_t st) {
+  const bool bn128 = bn == 128;
+  if (bm == 128) {
+    // the single-buffer 128x128 tile needs > 128 VGPRs: 3 workgroups per CU instead of 4
+    if (bn128) launch_ig<T, 128, 128, false, PRO, (OCC == 4 ? 3 : OCC), BW>(p, maxM, st);
+    else launch_ig<T, 128, 64, false, PRO, OCC, BW>(p, maxM, st);
+  } else {
+    if (bn128) launch_ig<T, 64, 128, false, PRO, OCC, BW>(p, maxM, st);
+    else launch_ig<T, 64, 64, false, PRO, OCC, BW>(p, maxM, st);
+  }
+}
+
+// BN-backward epilogue (+ apply prologue) variants (dgrad only: no stem, no BN+ReLU prologue)
+template <typename T, int OCC, int APB>
+static void dispatch_ig_bwd1(const IgParams& p, int maxM, int bm, int bn, hipStream_t st) {
+  if constexpr (sizeof(T) == 2 && !(APB & kFp8Bit)) {
+    if (p.bb.yx) {  // y recomputed in the epilogue (block-output BN: mask bits, + the downsample branch)
+      if (bwd_variant(p.bb) == 4) dispatch_ig<T, false, OCC, 4 | APB | kYrecBit>(p, maxM, bm, bn, st);
+      else dispatch_ig<T, false, OCC, 3 | APB | kYrecBit>(p, maxM, bm, bn, st);
+      return;
+    }
+  }
+  switch (bwd_variant(p.bb)) {
+    case 2: dispatch_ig<T, false, OCC, 2 | APB>(p, maxM, bm, bn, st); break;
+    case 3: dispatch_ig<T, false, OCC, 3 | APB>(p, maxM, bm, bn, st); break;
+    case 4: dispatch_ig<T, false, OCC, 4 | APB>(p, maxM, bm, bn, st); break;
+    default: dispatch_ig<T, false, OCC, APB>(p, maxM, bm, bn, st);
+  }
+}
+
+template <typename T, int OCC>
+static void dispatch_ig_bwd(const IgParams& p, int maxM, int bm, int bn, hipStream_t st) {
+  if (p.ap.y) dispatch_ig_bwd1<T, OCC, kApplyBit>(p, maxM, bm, bn, st);
+  else dispatch_ig_bwd1<T, OCC, 0>(p, maxM, bm, bn, st);
+}
+
+// the register-staged kernel for forward / dgrad params (the tail of run_ig): smallk = every phase's K
+// within policy key 7
+template <typename T>
+static int launch_ig_staged(const IgParams& p, int maxM, bool smallk, int bm, int bn, hipStream_t st) {
+  if (p.stem) {
+    if (p.N != 64 || bm != 128) { set_error("igemm: stem expects 64 output channels"); return ARGUS_ERR_SHAPE; }
+    launch_ig<T, 128, 64, true, false, 4>(p, maxM, st);  // single buffer (convbench B=64: 214 -> 179 us)
+  } else if (p.pro_scale) {
+    if (smallk) dispatch_ig<T, true, 4>(p, maxM, bm, bn, st);
+    else dispatch_ig<T, true, 2>(p, maxM, bm, bn, st);
+  } else if (p.bb.mode || p.ap.y) {
+    if (smallk && (*p.pol)[kBwdSmallKOcc] == 3) dispatch_ig_bwd<T, 3>(p, maxM, bm, bn, st);
+    else if (smallk) dispatch_ig_bwd<T, 4>(p, maxM, bm, bn, st);
+    else dispatch_ig_bwd<T, 2>(p, maxM, bm, bn, st);
+  } else {
+    if (smallk) dispatch_ig<T, false, 4>(p, maxM, bm, bn, st);
+    else dispatch_ig<T, false, 2>(p, maxM, bm, bn, st);
+  }
+  return check_launch("igemm_kernel");
+}
+
+struct WgPlan {
+  int bm, bn, mt, nt, splits, pps, kstep;
+  int N;
+};
+
+template <typename T, int BM, int BN, bool STEM, bool PRO, bool FAST, bool AP>
+static const char* wg_name() {
+  static const std::string s = std::string("argus::wgrad_kernel<") + elem_name<T>() + ", " + std::to_string(BM) +
+                               ", " + std::to_string(BN) + ", " + bool_name(STEM) + ", " + bool_name(PRO) + ", " +
+                               bool_name(FAST) + ", " + bool_name(AP) + ">";
+  return s.c_str();
+}
+
+template <typename T, int BM, int BN, bool STEM, bool PRO, bool FAST, bool AP = false>
+static void launch_wg(const WgParams& p, const WgPlan& pl, hipStream_t st) {
+  timed_launch(wg_name<T, BM, BN, STEM, PRO, FAST, AP>(), wgrad_kernel<T, BM, BN, STEM, PRO, FAST, AP>,
+               dim3(pl.mt * pl.nt * pl.splits), dim3(256), st, p);
+}
+
+template <typename T, bool PRO, bool FAST, bool AP = false>
+static void dispatch_wg_tiles(const WgParams& p, const WgPlan& pl, hipStream_t st) {
+  if (pl.bm == 128 && pl.bn == 128) launch_wg<T, 128, 128, false, PRO, FAST, AP>(p, pl, st);
+  else if (pl.bm == 128) launch_wg<T, 128, 64, false, PRO, FAST, AP>(p, pl, st);
+  else if (pl.bn == 128) launch_wg<T, 64, 128, false, PRO, FAST, AP>(p, pl, st);
+  else launch_wg<T, 64, 64, false, PRO, FAST, AP>(p, pl, st);
+}
+
+template <typename T>
+static void dispatch_wg(const WgParams& p, const WgPlan& pl, hipStream_t st) {
+  // FAST pixel indexing: every k-step lies in one image and rows tile the k-step evenly
+  const int bkp = pl.kstep;
+  const bool fast = (p.Ho * p.Wo) % bkp == 0 && (p.Wo % bkp == 0 || bkp % p.Wo == 0);
+  if (p.stem) {  // stem: M = 64 channels, N = 256; with the BN-backward apply of dy staged (AP) or not
+    if (p.ap_y) {
+      if (fast) launch_wg<T, 64, 128, true, false, true, true>(p, pl, st);
+      else launch_wg<T, 64, 128, true, false, false, true>(p, pl, st);
+    } else {
+      if (fast) launch_wg<T, 64, 128, true, false, true>(p, pl, st);
+      else launch_wg<T, 64, 128, true, false, false>(p, pl, st);
+    }
+  } else if (p.ap_y) {  // the BN-backward apply of dy staged from dm (argus_conv_wgrad_apply)
+    if (fast) dispatch_wg_tiles<T, false, true, true>(p, pl, st);
+    else dispatch_wg_tiles<T, false, false, true>(p, pl, st);
+  } else if (p.pro_scale) {
+    if (fast) dispatch_wg_tiles<T, true, true>(p, pl, st);
+    else dispatch_wg_tiles<T, true, false>(p, pl, st);
+  } else {
+    if (fast) dispatch_wg_tiles<T, false, true>(p, pl, st);
+    else dispatch_wg_tiles<T, false, false>(p, pl, st);
+  }
+}
+
+// The bf16x3 instantiations (element tag f32x3; policy key 53) live in a translation unit of their own,
+// conv_x3.hip, which includes this file with ARGUS_CONV_X3_TU defined and compiles the code above plus
+// these two launchers; the build compiles both units in parallel.
+int igemm_x3_launch(const IgParams& p, int maxM, bool smallk, int bm, int bn, hipStream_t st);
+void wgrad_x3_launch(const WgParams& p, const WgPlan& pl, hipStream_t st);
+
+#ifdef ARGUS_CONV_X3_TU
+int igemm_x3_launch(const IgParams& p, int maxM, bool smallk, int bm, int bn, hipStream_t st) {
+  return launch_ig_staged<f32x3>(p, maxM, smallk, bm, bn, st);
+}
+void wgrad_x3_launch(const WgParams& p, const WgPlan& pl, hipStream_t st) { dispatch_wg<f32x3>(p, pl, st); }
+#else
 
 // ------------------------------------------------------------------------------------------------
 // layout kernels
@@ -1178,62 +1445,6 @@ static int check_desc(const argus_conv_desc& d) {
   return ARGUS_OK;
 }
 
-template <typename T, int BM, int BN, bool STEM, bool PRO, int OCC, int BW>
-static const char* ig_name() {
-  static const std::string s = std::string("argus::igemm_kernel<") + type_name<T>() + ", " + std::to_string(BM) +
-                               ", " + std::to_string(BN) + ", " + bool_name(STEM) + ", " + bool_name(PRO) + ", " +
-                               std::to_string(OCC) + ", " + std::to_string(BW) + ">";
-  return s.c_str();
-}
-
-template <typename T, int BM, int BN, bool STEM, bool PRO, int OCC, int BW = 0>
-static void launch_ig(const IgParams& p0, int maxM, hipStream_t st) {
-  IgParams p = p0;
-  plan_fin(p, BM);
-  plan_ffin(p, BM);
-  const int ntiles = p.N / BN;
-  dim3 grid(cdiv(maxM, BM) * ntiles, 1, p.nphase);
-  timed_launch(ig_name<T, BM, BN, STEM, PRO, OCC, BW>(), igemm_kernel<T, BM, BN, STEM, PRO, OCC, BW>, grid,
-               dim3(256), st, p);
-}
-
-template <typename T, bool PRO, int OCC, int BW = 0>
-static void dispatch_ig(const IgParams& p, int maxM, int bm, int bn, hipStream_t st) {
-  const bool bn128 = bn == 128;
-  if (bm == 128) {
-    // the single-buffer 128x128 tile needs > 128 VGPRs: 3 workgroups per CU instead of 4
-    if (bn128) launch_ig<T, 128, 128, false, PRO, (OCC == 4 ? 3 : OCC), BW>(p, maxM, st);
-    else launch_ig<T, 128, 64, false, PRO, OCC, BW>(p, maxM, st);
-  } else {
-    if (bn128) launch_ig<T, 64, 128, false, PRO, OCC, BW>(p, maxM, st);
-    else launch_ig<T, 64, 64, false, PRO, OCC, BW>(p, maxM, st);
-  }
-}
-
-// BN-backward epilogue (+ apply prologue) variants (dgrad only: no stem, no BN+ReLU prologue)
-template <typename T, int OCC, int APB>
-static void dispatch_ig_bwd1(const IgParams& p, int maxM, int bm, int bn, hipStream_t st) {
-  if constexpr (sizeof(T) == 2 && !(APB & kFp8Bit)) {
-    if (p.bb.yx) {  // y recomputed in the epilogue (block-output BN: mask bits, + the downsample branch)
-      if (bwd_variant(p.bb) == 4) dispatch_ig<T, false, OCC, 4 | APB | kYrecBit>(p, maxM, bm, bn, st);
-      else dispatch_ig<T, false, OCC, 3 | APB | kYrecBit>(p, maxM, bm, bn, st);
-      return;
-    }
-  }
-  switch (bwd_variant(p.bb)) {
-    case 2: dispatch_ig<T, false, OCC, 2 | APB>(p, maxM, bm, bn, st); break;
-    case 3: dispatch_ig<T, false, OCC, 3 | APB>(p, maxM, bm, bn, st); break;
-    case 4: dispatch_ig<T, false, OCC, 4 | APB>(p, maxM, bm, bn, st); break;
-    default: dispatch_ig<T, false, OCC, APB>(p, maxM, bm, bn, st);
-  }
-}
-
-template <typename T, int OCC>
-static void dispatch_ig_bwd(const IgParams& p, int maxM, int bm, int bn, hipStream_t st) {
-  if (p.ap.y) dispatch_ig_bwd1<T, OCC, kApplyBit>(p, maxM, bm, bn, st);
-  else dispatch_ig_bwd1<T, OCC, 0>(p, maxM, bm, bn, st);
-}
-
 // ------------------------------------------------------------------------------------------------
 // kernel-selection policy (argus_conv_policy_default): an immutable table + per-call overrides
 // ------------------------------------------------------------------------------------------------
@@ -1340,6 +1551,11 @@ static const Policy kDefaultPolicy = [] {
   //     BN epilogue + fold), layer 3 43.4 vs 43.9 us; engine A/B level at B=64 and B=256
   //     (profiles/r06d_*): off. The halo loop is not waiting on weight stages in flight
   p.v[kHaloDeepRing] = 0;
+  // 53: the passes of an ARGUS_F32 conv (1 forward | 2 data gradient | 4 weight gradient) that run the
+  //     bf16x3 split arithmetic (igemm.h) instead of the exact fp32 MFMA. 0: every caller that does not ask
+  //     keeps the exact path (the Python surface asks with compute_dtype="bf16x3": all three, 7).
+  //     Key 52 is left unknown (the ABI test pins it).
+  p.v[kF32Split] = 0;
   return p;
 }();
 
@@ -1411,21 +1627,10 @@ static int run_ig(const IgParams& p, hipStream_t st, int bm, int bn) {
     else dispatch_ig<T, false, 2, kOutBit>(p, maxM, bm, bn, st);
     return check_launch("igemm_kernel");
   }
-  if (p.stem) {
-    if (p.N != 64 || bm != 128) { set_error("igemm: stem expects 64 output channels"); return ARGUS_ERR_SHAPE; }
-    launch_ig<T, 128, 64, true, false, 4>(p, maxM, st);  // single buffer (convbench B=64: 214 -> 179 us)
-  } else if (p.pro_scale) {
-    if (smallk) dispatch_ig<T, true, 4>(p, maxM, bm, bn, st);
-    else dispatch_ig<T, true, 2>(p, maxM, bm, bn, st);
-  } else if (p.bb.mode || p.ap.y) {
-    if (smallk && (*p.pol)[kBwdSmallKOcc] == 3) dispatch_ig_bwd<T, 3>(p, maxM, bm, bn, st);
-    else if (smallk) dispatch_ig_bwd<T, 4>(p, maxM, bm, bn, st);
-    else dispatch_ig_bwd<T, 2>(p, maxM, bm, bn, st);
-  } else {
-    if (smallk) dispatch_ig<T, false, 4>(p, maxM, bm, bn, st);
-    else dispatch_ig<T, false, 2>(p, maxM, bm, bn, st);
+  if constexpr (sizeof(T) == 4) {  // key 53: this pass of an fp32 conv on the bf16x3 split arithmetic
+    if ((*p.pol)[kF32Split] & (p.fwd ? 1 : 2)) return igemm_x3_launch(p, maxM, smallk, bm, bn, st);
   }
-  return check_launch("igemm_kernel");
+  return launch_ig_staged<T>(p, maxM, smallk, bm, bn, st);
 }
 
 // column tile of pass {0 fwd, 1 dgrad, 2 wgrad} (policy keys 3..5 force 64 | 128)
@@ -1868,11 +2073,6 @@ int conv_x8_ok(const argus_conv_desc& d, int pass) {
   return conv3x3_halo_x8_ok(p) ? 1 : 0;
 }
 
-struct WgPlan {
-  int bm, bn, mt, nt, splits, pps, kstep;
-  int N;
-};
-
 // ap: the BN-backward-apply form (argus_conv_wgrad_apply), which may pick another DMA tile width
 static WgPlan wgrad_plan(const argus_conv_desc& d, int dtype, bool ap = false) {
   const Policy pol = policy_of(d);
@@ -1926,53 +2126,6 @@ size_t conv_wgrad_ws(const argus_conv_desc& d, int dtype) {
   return b;
 }
 
-template <typename T, int BM, int BN, bool STEM, bool PRO, bool FAST, bool AP>
-static const char* wg_name() {
-  static const std::string s = std::string("argus::wgrad_kernel<") + type_name<T>() + ", " + std::to_string(BM) +
-                               ", " + std::to_string(BN) + ", " + bool_name(STEM) + ", " + bool_name(PRO) + ", " +
-                               bool_name(FAST) + ", " + bool_name(AP) + ">";
-  return s.c_str();
-}
-
-template <typename T, int BM, int BN, bool STEM, bool PRO, bool FAST, bool AP = false>
-static void launch_wg(const WgParams& p, const WgPlan& pl, hipStream_t st) {
-  timed_launch(wg_name<T, BM, BN, STEM, PRO, FAST, AP>(), wgrad_kernel<T, BM, BN, STEM, PRO, FAST, AP>,
-               dim3(pl.mt * pl.nt * pl.splits), dim3(256), st, p);
-}
-
-template <typename T, bool PRO, bool FAST, bool AP = false>
-static void dispatch_wg_tiles(const WgParams& p, const WgPlan& pl, hipStream_t st) {
-  if (pl.bm == 128 && pl.bn == 128) launch_wg<T, 128, 128, false, PRO, FAST, AP>(p, pl, st);
-  else if (pl.bm == 128) launch_wg<T, 128, 64, false, PRO, FAST, AP>(p, pl, st);
-  else if (pl.bn == 128) launch_wg<T, 64, 128, false, PRO, FAST, AP>(p, pl, st);
-  else launch_wg<T, 64, 64, false, PRO, FAST, AP>(p, pl, st);
-}
-
-template <typename T>
-static void dispatch_wg(const WgParams& p, const WgPlan& pl, hipStream_t st) {
-  // FAST pixel indexing: every k-step lies in one image and rows tile the k-step evenly
-  const int bkp = pl.kstep;
-  const bool fast = (p.Ho * p.Wo) % bkp == 0 && (p.Wo % bkp == 0 || bkp % p.Wo == 0);
-  if (p.stem) {  // stem: M = 64 channels, N = 256; with the BN-backward apply of dy staged (AP) or not
-    if (p.ap_y) {
-      if (fast) launch_wg<T, 64, 128, true, false, true, true>(p, pl, st);
-      else launch_wg<T, 64, 128, true, false, false, true>(p, pl, st);
-    } else {
-      if (fast) launch_wg<T, 64, 128, true, false, true>(p, pl, st);
-      else launch_wg<T, 64, 128, true, false, false>(p, pl, st);
-    }
-  } else if (p.ap_y) {  // the BN-backward apply of dy staged from dm (argus_conv_wgrad_apply)
-    if (fast) dispatch_wg_tiles<T, false, true, true>(p, pl, st);
-    else dispatch_wg_tiles<T, false, false, true>(p, pl, st);
-  } else if (p.pro_scale) {
-    if (fast) dispatch_wg_tiles<T, true, true>(p, pl, st);
-    else dispatch_wg_tiles<T, true, false>(p, pl, st);
-  } else {
-    if (fast) dispatch_wg_tiles<T, false, true>(p, pl, st);
-    else dispatch_wg_tiles<T, false, false>(p, pl, st);
-  }
-}
-
 // ap != nullptr: argus_conv_wgrad_apply (dy staged as ca*dm + cb*y + cc from dm = `dy`)
 static int conv_wgrad_impl(const argus_conv_desc& d, int dtype, const void* x, const float* sc, const float* sh,
                            const void* dy, const argus_bn_bwd_prologue* ap, float* dw, void* ws, size_t ws_bytes,
@@ -2012,12 +2165,14 @@ static int conv_wgrad_impl(const argus_conv_desc& d, int dtype, const void* x, c
     if (int e = check_launch("wgrad_dma_kernel")) return e;
   } else if (ap) {  // the register-staged kernel stages the apply; no halo / glds variant does
     if (dtype == ARGUS_BF16) dispatch_wg<bf16>(p, pl, st);
+    else if (pol[kF32Split] & 4) wgrad_x3_launch(p, pl, st);  // key 53: the bf16x3 split arithmetic
     else dispatch_wg<float>(p, pl, st);
     if (int e = check_launch("wgrad_kernel")) return e;
   } else if (wgrad3x3_halo_launch(d, dtype, x, sc, sh, dy, ws, ws_bytes, &splits, st)) {
     if (int e = check_launch("wgrad3x3_halo_kernel")) return e;
   } else {
     if (dtype == ARGUS_BF16) dispatch_wg<bf16>(p, pl, st);
+    else if (pol[kF32Split] & 4) wgrad_x3_launch(p, pl, st);  // key 53: the bf16x3 split arithmetic
     else dispatch_wg<float>(p, pl, st);
     if (int e = check_launch("wgrad_kernel")) return e;
   }
@@ -2135,5 +2290,7 @@ int images_to_nhwc4(int dtype, int64_t nimg, int h, int w, const float* x, void*
 int images_u8_to_nhwc4(int dtype, int64_t nimg, int h, int w, const uint8_t* x, void* out, hipStream_t st) {
   return launch_images(dtype, nimg, h, w, x, out, st);
 }
+
+#endif  // !ARGUS_CONV_X3_TU
 
 }  // namespace argus

@@ -133,6 +133,32 @@ template <> struct Mma<float> {
   }
 };
 
+// bf16x3 split arithmetic of the fp32 conv GEMMs (policy key 53): the stand-in for the TF32 / xf32 matrix
+// rate gfx950 does not have. Tensors, accumulators, epilogues and statistics stay fp32; each GEMM operand
+// element x is split, while it is staged to LDS (after any prologue), into hi = bf16(x) and
+// lo = bf16(x - hi), and a K = 32 block is accumulated by three v_mfma_f32_16x16x32_bf16 in the fixed
+// order hi*hi, hi*lo, lo*hi instead of eight v_mfma_f32_16x16x4_f32. The bf16 products are exact in the
+// fp32 accumulator; dropped are the two operand residuals (<= 2^-16 |x| each) and lo*lo:
+// |error| <= 3 * 2^-16 * sum |a*b| per output, before the accumulation's own rounding.
+// Both casts round to nearest even (v_cvt_pk_bf16_f32: NaN stays NaN); x - hi is exact in fp32; zero
+// (padding) splits into two zeros. Edge cases: an infinite input gives hi = inf, lo = inf - inf = NaN, and a
+// finite input above the largest bf16 (about 3.39e38) rounds hi to inf and leaves lo = -inf, so hi*b + lo*b
+// is inf - inf: such outputs are NaN where the exact kernels give inf or a finite value. A lo part below the smallest normal bf16
+// (|x| < ~2^-118) may be flushed to zero by the MFMA; the result then carries x's bf16 rounding alone.
+// f32x3 is the kernels' element tag of this variant: storage float (Elem<f32x3>::type).
+struct f32x3 { float v; };
+template <typename TT> struct Elem { using type = TT; static constexpr bool X3 = false; };
+template <> struct Elem<f32x3> { using type = float; static constexpr bool X3 = true; };
+
+ARGUS_DEV void split_x3(u32x4 v, uint2& hi, uint2& lo) {
+  float f[4];
+  unpack(v, f);
+  hi.x = pack2_bf16(f[0], f[1]);
+  hi.y = pack2_bf16(f[2], f[3]);
+  lo.x = pack2_bf16(f[0] - __uint_as_float(hi.x << 16), f[1] - __uint_as_float(hi.x & 0xffff0000u));
+  lo.y = pack2_bf16(f[2] - __uint_as_float(hi.y << 16), f[3] - __uint_as_float(hi.y & 0xffff0000u));
+}
+
 ARGUS_DEV int swz8(int row) { return (row >> 1) & 7; }
 
 // Per-thread state of the BN-backward epilogue: a thread owns one 16-byte channel chunk (fixed

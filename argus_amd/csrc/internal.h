@@ -65,7 +65,8 @@ enum TuneKey : int {
   kWgradDmaStages = 48,   // LDS ring stages of the 128 x 256 apply DMA weight gradient (2..5)
   kDgradApMaxCols = 49,   // 1x1 dgrads stage the apply prologue up to this many 128-column tiles (0: any)
   kHaloDeepRing = 51,     // 3x3 halo fwd / dgrad (128 columns, <= 384 halo positions): four weight stages (1 on)
-  kNumTuneKeys = 52
+  kF32Split = 53,         // ARGUS_F32: passes on the bf16x3 split arithmetic (1 fwd | 2 dgrad | 4 wgrad); 52 is no key
+  kNumTuneKeys = 54
 };
 struct Policy {
   int v[kNumTuneKeys];

@@ -73,12 +73,18 @@ class ResNetEngine:
 
     def __init__(self, n_cams: int, resnet_output_dim: int, dtype: str, device: torch.device,
                  tuning: dict | None = None):
-        if dtype not in ("fp32", "bf16", "fp8"):
-            raise ValueError(f"compute dtype must be 'fp32', 'bf16' or 'fp8', got {dtype!r}")
+        if dtype not in ("fp32", "bf16x3", "bf16", "fp8"):
+            raise ValueError(f"compute dtype must be 'fp32', 'bf16x3', 'bf16' or 'fp8', got {dtype!r}")
         self.L = lib()
         # per-call overrides of the library's kernel-selection policy, attached to every conv descriptor
         # of this engine (argus_conv_desc.tuning; None = the library defaults, the benched selection)
         self.tuning = dict(tuning) if tuning else None
+        # "bf16x3": the fp32 engine (fp32 tensors, fused-prologue schedule) whose conv GEMMs run the split
+        # arithmetic hi*hi + hi*lo + lo*hi on the bf16 MFMA (policy key 53, all three passes; an explicit
+        # entry for 53 in `tuning` wins). gfx950 has no TF32 / xf32 MFMA: this is the mode that
+        # torch.set_float32_matmul_precision("high") stands for here.
+        if dtype == "bf16x3":
+            self.tuning = {53: 7, **(self.tuning or {})}
         self.n_cams = n_cams
         self.rdim = resnet_output_dim
         self.dtype = dtype

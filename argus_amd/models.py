@@ -15,7 +15,11 @@ forward and backward are the native schedule in ``argus_amd.engine`` (hand-writt
 Pretrained ImageNet weights (``weights="DEFAULT"``) are not downloadable offline: seeded init, or
 load a local ``.pth``.
 
-Extension: ``compute_dtype`` ("fp32" — parity path, fp32 activations and exact-fp32 MFMA; "bf16" —
+Extension: ``compute_dtype`` ("fp32" — parity path, fp32 activations and exact-fp32 MFMA; "bf16x3" —
+the fp32 path whose conv GEMMs split each operand into two bf16 parts and accumulate hi*hi + hi*lo +
+lo*hi in fp32 on the bf16 MFMA (policy key 53 = 7 merged into ``kernel_tuning``; an explicit entry for
+53 wins): what ``torch.set_float32_matmul_precision("high")`` stands for on gfx950, which has no
+TF32 / xf32 MFMA; "bf16" —
 throughput path, bf16 activations/weights with fp32 accumulation, statistics and head; "fp8" — the
 bf16 path whose conv forward and data-gradient GEMMs take OCP MX-fp8 operands (e4m3 + E8M0 block
 scales, BASELINE configs[4]) where the channel count allows). The reference's ``--amp`` (fp16

@@ -1,6 +1,6 @@
 """Forward-latency benchmark — the MI355X counterpart of the reference's ``scripts/timing.py``.
 
-    python -m argus_amd.timing [--trials 100] [--batch 2] [--hw 256 256] [--dtype fp32|bf16]
+    python -m argus_amd.timing [--trials 100] [--batch 2] [--hw 256 256] [--dtype fp32|bf16x3|bf16]
                                [--eval] [--no-graph]
 
 Reference semantics (scripts/timing.py:10-48): ``NCameraCNN(n_cams=2)`` in fp32 on the GPU, left in
@@ -78,7 +78,7 @@ def main() -> None:
     ap.add_argument("--trials", type=int, default=100)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--hw", type=int, nargs=2, default=(256, 256))
-    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16x3", "bf16"])
     ap.add_argument("--eval", action="store_true", help="eval-mode BN (running statistics)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a replayed hipGraph")
     a = ap.parse_args()

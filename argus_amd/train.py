@@ -82,9 +82,18 @@ class TrainConfig:
     wandb_project: str = "argus-estimator"
     wandb_log: bool = True
     num_workers: int = -1  # extension: DataLoader workers (-1: the reference's 16 / 8 per rank, capped)
+    # extension: "highest" (default) keeps the exact fp32 MFMA of the parity path; "high" selects
+    # compute_dtype="bf16x3" when amp is false (fp32 tensors, conv GEMMs as three bf16 MFMA products of
+    # split operands, the documented meaning of torch.set_float32_matmul_precision("high")). The reference
+    # itself sets "high" (argus/train.py:26) and so trains on TF32 tensor cores; gfx950 has no TF32 / xf32
+    # MFMA and exact fp32 stays the default here. Any other value is rejected.
+    float32_matmul_precision: str = "highest"
 
     def __post_init__(self) -> None:
         assert isinstance(self.save_dir, str)
+        if self.float32_matmul_precision not in ("highest", "high"):
+            raise ValueError(f"float32_matmul_precision must be 'highest' or 'high', got "
+                             f"{self.float32_matmul_precision!r}")
         if not os.path.exists(self.save_dir):
             if os.path.exists(ROOT + "/" + self.save_dir):
                 object.__setattr__(self, "save_dir", ROOT + "/" + self.save_dir)
@@ -194,7 +203,8 @@ def initialize_training(cfg: TrainConfig, rank: int = 0, world: int = 1):
     train_loader, val_loader, train_sampler, val_sampler = make_loaders(cfg, train_ds, val_ds, rank, world)
     distributed = world > 1
 
-    model = NCameraCNN(cfg.model_config, compute_dtype="bf16" if cfg.amp else "fp32").to(device)
+    fp32_mode = "bf16x3" if cfg.float32_matmul_precision == "high" else "fp32"
+    model = NCameraCNN(cfg.model_config, compute_dtype="bf16" if cfg.amp else fp32_mode).to(device)
     if distributed:  # DDP's constructor broadcast (train.py:199): every rank starts from rank 0's weights
         for t in list(model.parameters()) + list(model.buffers()):
             dist.broadcast(t.data, src=0)
@@ -331,6 +341,8 @@ def parse_args(argv=None) -> TrainConfig:
     ns = vars(ap.parse_args(argv))
     if ns.get("dataset_config.dataset_path") is None:
         ap.error("--dataset-config.dataset-path is required")
+    if ns.get("float32_matmul_precision") not in (None, "highest", "high"):
+        ap.error("--float32-matmul-precision must be 'highest' or 'high'")
     return _build(TrainConfig, ns)
 
 

@@ -53,7 +53,8 @@ class ValConfig:
 
 def load_model(model_path: str, model_config: NCameraCNNConfig | None = None, device="cuda",
                compute_dtype: str = "fp32") -> NCameraCNN:
-    """NCameraCNN with the weights of a reference-format ``.pth`` (plain, DDP or compiled keys)."""
+    """NCameraCNN with the weights of a reference-format ``.pth`` (plain, DDP or compiled keys);
+    ``compute_dtype``: "fp32", "bf16x3", "bf16" or "fp8" (argus_amd.models)."""
     model = NCameraCNN(model_config, compute_dtype=compute_dtype)
     sd = torch.load(model_path, map_location="cpu", weights_only=True)
     model.load_state_dict(sd)

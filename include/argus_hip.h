@@ -282,7 +282,17 @@ int argus_conv_dgrad_bn_x8(const argus_conv_desc* d, const void* dy8, const void
  * 128-column tiles for which a 1x1 data gradient stages its apply prologue itself (more: dy is
  * materialised first; 0 = always staged; default 4); key 51 the 3x3 halo forward / data gradient with a
  * four-stage weight ring where the tile's halo fits 384 positions (1) or the three-stage ring (0,
- * default). Key 50 was removed and is unknown, like key 30.
+ * default); key 53 (ABI 21) the passes of an ARGUS_F32 conv that run the bf16x3 split arithmetic (bits: 1
+ * forward, 2 data gradient, 4 weight gradient; default 0 = the exact fp32 MFMA): tensors, accumulators,
+ * epilogues and BN statistics stay fp32, each GEMM operand is split while staged into hi = bf16(x) and
+ * lo = bf16(x - hi), and hi*hi + hi*lo + lo*hi is accumulated in fp32 on the bf16 MFMA, in that fixed
+ * order (deterministic), |error| <= 4 * 2^-16 * sum |a*b| per output. gfx950 has no TF32 / xf32 MFMA:
+ * this is what torch.set_float32_matmul_precision("high") stands for here. Honoured by every conv entry
+ * point given ARGUS_F32 (argus_conv_fwd, _fwd_apply_out, _fwd_fin, argus_conv_dgrad, _dgrad_bn,
+ * argus_conv_wgrad, _wgrad_apply), ignored for ARGUS_BF16 / ARGUS_FP8; weight prep, the statistics /
+ * workspace queries and argus_conv_launch_info do not depend on it. Non-finite inputs and inputs above
+ * the bf16 maximum (~3.39e38) give NaN; lo parts that are bf16 subnormals may be flushed to zero.
+ * Key 50 was removed and is unknown, like key 30; key 52 is unknown.
  * (Keys scaled with the batch keep a smaller batch's kernel selection that of the larger one:
  * tests/test_gpu_parity.py stage-checks the benched configurations' kernels that way.) */
 int argus_conv_policy_default(int key);
