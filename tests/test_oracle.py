@@ -144,3 +144,69 @@ def test_trajectory_golden_pins_oracle():
     assert lrs == [s["lr"] for s in g["fp64"]["steps"]] and min(lrs) < c["lr"]
     for s32, s64 in zip(g["fp32"]["steps"], g["fp64"]["steps"]):
         assert max(abs(a - b) for a, b in zip(s32["loss"], s64["loss"])) < 1e-2
+
+
+def _regime_properties(name, pred, T, angle):
+    """Every sample sits where its regime says; the residual angle is the definition's own."""
+    th = pred[:, 3:].double().norm(dim=-1)
+    assert (math.pi - angle).min().item() > 5e-4, name  # the principal logarithm jumps at pi
+    if name == "generic":
+        assert (pred[:, :3].abs().amax(-1) > 0).all() and (th > 1e-2).all() and (angle > 1e-2).all()
+        assert (T[:, :3].abs().amax(-1) > 0).all() and (T[:, 3:6].abs().amax(-1) > 0).all()
+    elif name == "pred_small_angle":
+        assert th.min() == 0 and ((th > 0.9e-4) & (th < 1e-4)).any() and ((th > 1e-4) & (th < 1.1e-4)).any()
+    elif name == "residual_small":
+        n = torch.sin(angle / 2)
+        assert angle.min() < 1e-7 and ((n > 0.98e-4) & (n < 1e-4)).any() and ((n > 1e-4) & (n < 1.02e-4)).any()
+    elif name == "residual_near_pi":
+        d = math.pi - angle
+        assert ((d - 1e-3).abs() < 1e-5).sum() == 4 and ((d - 1e-2).abs() < 1e-5).sum() == 4
+        assert (T[:, :3].abs().amax(-1) > 0).all()
+    elif name == "pred_beyond_pi":
+        assert (th > math.pi).all() and (th > 2 * math.pi).any()
+        assert (angle[-4:] < 1.9e-4).all() and (angle[-4:] > 1e-5).all()  # n < 1e-4 with w < 0
+    elif name == "large_translation":
+        assert (pred[:, :3].double().norm(dim=-1) > 30).all() and (T[:, :3].double().norm(dim=-1) > 30).all()
+    elif name == "target_quat_scaled":
+        s = T[:, 3:].double().norm(dim=-1)
+        n = s * torch.sin(angle / 2)
+        assert ((s - 1).abs() > 0.4).sum() >= 10 and (T[:, 6] < 0).any()
+        assert ((n < 1e-4) & ((s - 1).abs() > 0.4)).sum() >= 4 and (n > 1e-4).any()
+
+
+def test_loss_and_grad_match_the_definition_in_every_regime():
+    """oracle/se3.py's closed forms (Rodrigues, J_l, atan, their Taylor branches and thresholds) against
+    the matrix exponential and the principal matrix logarithm at 40 digits, gradient by central
+    differences at that precision (tests/se3_cases.py). Bars: se3_cases.BARS, 4x the measured discrepancy."""
+    from tests import se3_cases
+
+    assert list(se3_cases.BARS) == list(se3_cases.regimes())
+    for name, (pred, T) in se3_cases.regimes().items():
+        d_loss, d_grad, angle = se3_cases.definition_results(name)
+        _regime_properties(name, pred, T, angle)
+        o_loss, o_grad = se3.loss_and_grad(pred, T, mean=False)
+        bar = se3_cases.BARS[name]
+        e_loss = (o_loss - d_loss).abs()
+        e_grad = (o_grad - d_grad).abs().amax(-1)
+        g_inf = d_grad.abs().amax(-1)
+        print(name, "loss: rel", (e_loss / d_loss.abs())[d_loss.abs() >= se3_cases.SMALL].tolist(),
+              "abs", e_loss[d_loss.abs() < se3_cases.SMALL].tolist())
+        print(name, "grad: rel", (e_grad / g_inf)[g_inf >= se3_cases.SMALL].tolist(),
+              "abs", e_grad[g_inf < se3_cases.SMALL].tolist())
+        assert (e_loss <= bar["r_loss"] * d_loss.abs() + bar["a_loss"]).all(), name
+        assert (e_grad <= bar["r_grad"] * g_inf + bar["a_grad"]).all(), name
+
+
+def test_se3_exp_matches_the_matrix_exponential():
+    from tests import se3_cases
+
+    for name in se3_cases.EXP_REGIMES:
+        xi = se3_cases.regimes()[name][0]
+        want = se3_cases.definition_exp(xi)
+        got = se3.se3_exp(xi.double())
+        bar = se3_cases.EXP_BARS[name]
+        e_t = (got[:, :3] - want[:, :3]).abs().amax(-1)
+        e_q = (got[:, 3:] - want[:, 3:]).abs().amax(-1)
+        print(name, "t", (e_t / want[:, :3].abs().amax(-1).clamp_min(1.0)).max().item(), "q", e_q.max().item())
+        assert (e_t <= bar["r_t"] * want[:, :3].abs().amax(-1).clamp_min(1.0)).all(), name
+        assert (e_q <= bar["a_q"]).all(), name
