@@ -96,6 +96,11 @@ SIGNATURES = {
     "argus_conv_weight_prep_batch": (_I, [_I, _I, _P, _I, _P]),
     "argus_conv_fwd": (_I, [_DESC, _I, _P, _P, _P, _P, _P, _P, _P]),
     "argus_conv_fwd_bn_out": (_I, [_DESC, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "argus_conv_fold_bn": (_I, [_DESC, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
+    "argus_conv_infer_splits": (_I, [_DESC, _I]),
+    "argus_conv_infer_max_splits": (_I, [_DESC, _I]),
+    "argus_conv_infer_workspace_bytes": (_SZ, [_DESC, _I, _I]),
+    "argus_conv_infer": (_I, [_DESC, _I, _P, _P, _P, _P, _I, _P, _I, _P, _SZ, _P]),
     "argus_conv_x8_ok": (_I, [_DESC, _I]),
     "argus_conv_fwd_stats_only_rows": (_I, [_DESC, _I]),
     "argus_conv_fwd_stats_only_tile": (_I, [_DESC, _I]),
@@ -182,7 +187,7 @@ class _Lib:
 
     def __getattr__(self, name: str):
         fn = getattr(self.dll, "argus_" + name)
-        if fn.restype is _I and not name.endswith(("rows", "tile", "version", "info", "default", "count")):
+        if fn.restype is _I and not name.endswith(("rows", "tile", "version", "info", "default", "count", "splits")):
             def call(*args, _fn=fn, _name=name):
                 rc = _fn(*args)
                 if rc != 0:

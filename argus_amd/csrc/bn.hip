@@ -172,10 +172,10 @@ __global__ void bn_eval_kernel(int C, const float* gamma, const float* beta, con
                                float eps, float* scale, float* shift) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float inv = 1.f / sqrtf(rv[c] + eps);
-  const float sc = gamma[c] * inv;
+  float sc, sh;
+  bn_eval_coeff(gamma, beta, rm, rv, eps, c, sc, sh);
   scale[c] = sc;
-  shift[c] = beta[c] - rm[c] * sc;
+  shift[c] = sh;
 }
 
 // ---- elementwise kernels: channel-chunk-stationary threads ---------------------------------------

@@ -34,6 +34,17 @@ ARGUS_DEV void store_wt2(double2* p, double2 v) {
   __hip_atomic_store(q + 1, (unsigned long long)__double_as_longlong(v.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Eval-mode BatchNorm as y*scale + shift from the running statistics of channel c: the one definition
+// behind argus_bn_eval_coeffs (bn_eval_kernel) and argus_conv_fold_bn (conv_infer.hip), whose bias and
+// weight scale are bit-identical to these by construction.
+ARGUS_DEV void bn_eval_coeff(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                             int c, float& scale, float& shift) {
+  const float inv = 1.f / sqrtf(rv[c] + eps);
+  const float sc = gamma[c] * inv;
+  scale = sc;
+  shift = beta[c] - rm[c] * sc;
+}
+
 // Every thread of the workgroup calls this (uniform). True in the workgroup that drew ticket n-1.
 ARGUS_DEV bool fin_ticket(unsigned* cnt_, unsigned n, int* flag) {
   fin_gu32* cnt = (fin_gu32*)cnt_;

@@ -122,6 +122,33 @@ size_t argus_conv_fwd_stat_part_bytes(const argus_conv_desc* d, int dtype, int s
   return (size_t)rows * d->k * 2 * sizeof(float) + (tile < 0 ? (size_t)rows * sizeof(int32_t) : 0);
 }
 
+int argus_conv_fold_bn(const argus_conv_desc* d, int dtype, const float* w_master, const int64_t* strides,
+                       const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                       float eps, void* w_fold, float* bias, argus_stream_t stream) {
+  if (!d || !w_master || !gamma || !beta || !running_mean || !running_var || !w_fold || !bias) {
+    set_error("conv_fold_bn: null argument");
+    return ARGUS_ERR_ARG;
+  }
+  return conv_fold_bn(*d, dtype, w_master, strides, gamma, beta, running_mean, running_var, eps, w_fold, bias,
+                      (hipStream_t)stream);
+}
+
+int argus_conv_infer_splits(const argus_conv_desc* d, int dtype) { return d ? conv_infer_splits(*d, dtype) : 0; }
+int argus_conv_infer_max_splits(const argus_conv_desc* d, int dtype) {
+  return d ? conv_infer_max_splits(*d, dtype) : 0;
+}
+size_t argus_conv_infer_workspace_bytes(const argus_conv_desc* d, int dtype, int splits) {
+  return d ? conv_infer_ws_bytes(*d, dtype, splits) : 0;
+}
+
+int argus_conv_infer(const argus_conv_desc* d, int dtype, const void* x, const void* w_fold, const float* bias,
+                     const void* res, int relu, void* out, int splits, void* workspace, size_t workspace_bytes,
+                     argus_stream_t stream) {
+  if (!d || !x || !w_fold || !bias || !out) { set_error("conv_infer: null argument"); return ARGUS_ERR_ARG; }
+  return conv_infer(*d, dtype, x, w_fold, bias, res, relu, out, splits, workspace, workspace_bytes,
+                    (hipStream_t)stream);
+}
+
 int argus_conv_policy_default(int key) { return policy_default(key); }
 
 int argus_conv_launch_info(const argus_conv_desc* d, int dtype, int pass, int64_t* flops) {

@@ -105,6 +105,15 @@ int conv_wgrad(const argus_conv_desc& d, int dtype, const void* x, const float* 
                hipStream_t st);
 int conv_weight_prep(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides,
                      void* wf, void* wd, hipStream_t st);
+// frozen inference (conv_infer.hip): BN fold, split choice / bound / workspace, forward
+int conv_fold_bn(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides, const float* gamma,
+                 const float* beta, const float* rm, const float* rv, float eps, void* wf, float* bias,
+                 hipStream_t st);
+int conv_infer_splits(const argus_conv_desc& d, int dtype);
+int conv_infer_max_splits(const argus_conv_desc& d, int dtype);
+size_t conv_infer_ws_bytes(const argus_conv_desc& d, int dtype, int splits);
+int conv_infer(const argus_conv_desc& d, int dtype, const void* x, const void* w, const float* bias, const void* res,
+               int relu, void* out, int splits, void* ws, size_t ws_bytes, hipStream_t st);
 int images_to_nhwc4(int dtype, int64_t nimg, int h, int w, const float* x, void* out,
                     hipStream_t st);
 int images_u8_to_nhwc4(int dtype, int64_t nimg, int h, int w, const uint8_t* x, void* out,

@@ -1,7 +1,7 @@
 """Forward-latency benchmark — the MI355X counterpart of the reference's ``scripts/timing.py``.
 
     python -m argus_amd.timing [--trials 100] [--batch 2] [--hw 256 256] [--dtype fp32|bf16x3|bf16]
-                               [--eval] [--no-graph]
+                               [--eval] [--no-graph] [--frozen]
 
 Reference semantics (scripts/timing.py:10-48): ``NCameraCNN(n_cams=2)`` in fp32 on the GPU, left in
 its default (train) mode — BatchNorm uses batch statistics — a fresh ``torch.rand((2, 6, 256, 256))``
@@ -12,6 +12,9 @@ The reference compiles the model with ``torch.compile(mode="reduce-overhead")``,
 captured device graph. The equivalent here is a hipGraph of the whole native forward (every HIP
 launch of ``ResNetEngine.forward`` on one captured stream), replayed per trial after the new batch is
 copied into the graph's static input buffer; ``--no-graph`` times eager launches instead.
+
+``--frozen`` times an ``argus_amd.infer.InferenceSession`` built from the model in eval mode instead (BN
+folded into the conv weights, one launch per conv, its own captured graph): the deployment path.
 
 One deliberate difference: the reference prints ``np.mean(runtime)`` — the last trial only
 (scripts/timing.py:48); this prints the mean (and median, min) over all timed trials.
@@ -29,8 +32,9 @@ from argus_amd.utils import time_torch_fn
 
 
 def forward_latency(trials: int = 100, batch: int = 2, hw=(256, 256), dtype: str = "fp32", train_mode: bool = True,
-                    graph: bool = True, device: str = "cuda") -> dict:
-    """Mean / median / min seconds of one NCameraCNN forward (no_grad) over ``trials`` timed trials."""
+                    graph: bool = True, device: str = "cuda", frozen: bool = False) -> dict:
+    """Mean / median / min seconds of one NCameraCNN forward (no_grad) over ``trials`` timed trials.
+    ``frozen``: the forward of an InferenceSession of the model in eval mode."""
     torch.manual_seed(0)
     cfg = NCameraCNNConfig(n_cams=2)
     model = NCameraCNN(cfg, compute_dtype=dtype).to(device)
@@ -38,7 +42,15 @@ def forward_latency(trials: int = 100, batch: int = 2, hw=(256, 256), dtype: str
     H, W = hw
     static_x = torch.rand((batch, cfg.n_cams * 3, H, W), device=device)
     first = None
-    if graph:
+    if frozen:
+        from argus_amd.infer import InferenceSession
+
+        session = InferenceSession(model.eval(), batch, (H, W), graph=graph)
+        train_mode = False
+
+        def run(x):
+            return session(x)
+    elif graph:
         # untimed warm-up (workspaces, weight-prep table), then capture on a side stream
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -68,9 +80,12 @@ def forward_latency(trials: int = 100, batch: int = 2, hw=(256, 256), dtype: str
         else:
             times.append(t)
     assert torch.isfinite(out).all()
-    return {"mean_s": statistics.fmean(times), "median_s": statistics.median(times), "min_s": min(times),
-            "first_call_s": first, "trials": trials, "batch": batch, "hw": list(hw), "dtype": dtype,
-            "mode": "train" if train_mode else "eval", "graph": graph}
+    r = {"mean_s": statistics.fmean(times), "median_s": statistics.median(times), "min_s": min(times),
+         "first_call_s": first, "trials": trials, "batch": batch, "hw": list(hw), "dtype": dtype,
+         "mode": "train" if train_mode else "eval", "graph": graph}
+    if frozen:
+        r["frozen"] = True
+    return r
 
 
 def main() -> None:
@@ -81,8 +96,10 @@ def main() -> None:
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16x3", "bf16"])
     ap.add_argument("--eval", action="store_true", help="eval-mode BN (running statistics)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a replayed hipGraph")
+    ap.add_argument("--frozen", action="store_true",
+                    help="time an InferenceSession of the eval-mode model (fp32 / bf16)")
     a = ap.parse_args()
-    r = forward_latency(a.trials, a.batch, tuple(a.hw), a.dtype, not a.eval, not a.no_graph)
+    r = forward_latency(a.trials, a.batch, tuple(a.hw), a.dtype, not a.eval, not a.no_graph, frozen=a.frozen)
     print(f"Forward pass took {r['mean_s']} seconds on average.")
     print(json.dumps(r))
 

@@ -59,7 +59,9 @@ def rotation_angle_error(pred: torch.Tensor, target: torch.Tensor) -> torch.Tens
 
 
 def get_pose(images: torch.Tensor, model: torch.nn.Module) -> torch.Tensor:
-    """Cube pose (B, 7), quaternion (x, y, z, w), from (B, 3*n_cams, H, W) images."""
+    """Cube pose (B, 7), quaternion (x, y, z, w), from (B, 3*n_cams, H, W) images. ``model`` is any callable
+    returning (B, 6) se(3) vectors: an ``NCameraCNN``, or an ``argus_amd.infer.InferenceSession`` of one (the
+    frozen deployment path; ``session.pose(images)`` is the same call)."""
     return se3_exp(model(images))
 
 

@@ -121,6 +121,40 @@ int argus_conv_fwd_apply_out(const argus_conv_desc* d, int dtype, const void* x,
 int argus_conv_fwd_bn_out(const argus_conv_desc* d, int dtype, const void* x, const void* w_fwd,
                           const float* scale, const float* shift, const void* res, const float* res_scale,
                           const float* res_shift, void* out, uint8_t* mask_bits, void* y, argus_stream_t stream);
+/* ---- frozen inference (ABI 21, added later without a version change: detect by symbol) ----------
+ * A deployed model's convolutions: eval-mode BatchNorm folded into the weights once, then one launch per
+ * conv. Together they replace nn.Conv2d + nn.BatchNorm2d.eval() [+ add] + nn.ReLU of torchvision's
+ * Bottleneck.forward (argus/models.py:43). Served: 1x1 (pad 0) and 3x3 (pad 1) convs of stride 1 or 2, c
+ * and k multiples of 64, any h x w, dtype ARGUS_F32 or ARGUS_BF16 (anything else: ARGUS_ERR_ARG); not the
+ * stem, which keeps argus_conv_fwd + argus_maxpool_fwd with argus_bn_eval_coeffs. Nothing here allocates
+ * or synchronises: every call can be captured into a graph.
+ *
+ * argus_conv_fold_bn: from the fp32 master weight (element strides as argus_conv_weight_prep; NULL = OHWI
+ * contiguous) and the BN parameters / running statistics, bias[k] (fp32) = the shift and
+ * w_fold[k][r][s][c] = T(w * scale[k]) (one fp32 multiply, round to nearest even; the w_fwd layout), with
+ * scale / shift bit-identical to argus_bn_eval_coeffs. */
+int argus_conv_fold_bn(const argus_conv_desc* d, int dtype, const float* w_master, const int64_t* strides,
+                       const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                       float eps, void* w_fold, float* bias, argus_stream_t stream);
+/* The reduction (r*s*c) of argus_conv_infer may be split over workgroups when its output tiles alone
+ * leave the chip idle. _splits: the library's choice for this shape (>= 1; 0 = shape / dtype not
+ * served); _max_splits: the largest accepted value = the k-steps of the reduction (r*s*c / 64 in bf16,
+ * / 32 in fp32); _workspace_bytes: what `splits` slices need (0 for splits <= 1): one uint32 ticket per
+ * output tile at the start of the workspace (padded to 256 bytes), then the fp32 slabs. */
+int argus_conv_infer_splits(const argus_conv_desc* d, int dtype);
+int argus_conv_infer_max_splits(const argus_conv_desc* d, int dtype);
+size_t argus_conv_infer_workspace_bytes(const argus_conv_desc* d, int dtype, int splits);
+/* out = [relu](conv(x, w_fold) + bias[k] [+ res]) over NHWC tensors; res (may be NULL) has out's layout and
+ * dtype; the sum is made in fp32 and rounded once. splits: 0 = argus_conv_infer_splits, 1 = no split (no
+ * workspace touched, workspace may be NULL), up to argus_conv_infer_max_splits: the slices' fp32 partial
+ * tiles are summed in slice order by the last-arriving workgroup of each output tile, so the result is
+ * bitwise reproducible for a given `splits`. The workspace (16-byte aligned) is caller-provided; its
+ * ticket words must be zero on entry - zero the workspace once - and every call leaves them zero. One
+ * workspace serves the launches of one stream in order, never two concurrent launches. */
+int argus_conv_infer(const argus_conv_desc* d, int dtype, const void* x, const void* w_fold, const float* bias,
+                     const void* res, int relu, void* out, int splits, void* workspace, size_t workspace_bytes,
+                     argus_stream_t stream);
+
 int argus_conv_fwd_stat_rows(const argus_conv_desc* d, int dtype);
 int argus_conv_fwd_stat_tile(const argus_conv_desc* d, int dtype);
 /* The partial layout (rows, tile as above) of a statistics-only argus_conv_fwd (y == NULL, no

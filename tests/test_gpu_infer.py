@@ -1,0 +1,274 @@
+"""GPU: frozen inference (argus_conv_fold_bn, argus_conv_infer, argus_amd.infer.InferenceSession).
+
+Kernel bars are the existing ones of tests/test_gpu_kernels.py: 2e-5 (fp32) / 1.5e-2 (bf16) of the reference's
+maximum magnitude against an fp64 F.conv2d on the operands as stored. The fold is checked bit for bit against
+argus_bn_eval_coeffs. The session is held to the fp64 oracle in eval mode with non-trivial running statistics:
+fp32 within 1e-4 absolute (the project's fp32 bar; the CPU fp32 oracle itself is 7e-6 from fp64 with this
+recipe at |pred| <= 13), bf16 within 2x the distance of the existing compute_dtype="bf16" model.eval() forward
+measured in the same test.
+"""
+import ctypes as C
+
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from argus_amd._lib import BF16, F32, ConvDesc, lib, ptr, stream
+
+pytestmark = pytest.mark.gpu
+
+TOL = {"fp32": 2e-5, "bf16": 1.5e-2}
+TDT = {"fp32": torch.float32, "bf16": torch.bfloat16}
+DT = {"fp32": F32, "bf16": BF16}
+
+
+def _desc(n, h, w, cin, cout, k, s):
+    p = 1 if k == 3 else 0
+    return ConvDesc(n, h, w, cin, cout, k, k, s, p, (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1, 0)
+
+
+def _bn_params(c, gen, cuda):
+    return [(0.5 + torch.rand(c, generator=gen)).to(cuda) for _ in range(4)]  # gamma, beta, mean, var in [0.5, 1.5)
+
+
+# ---- 1. fold: bit-exact against argus_bn_eval_coeffs ------------------------------------------------------
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+@pytest.mark.parametrize("cin,cout,k", [(64, 64, 1), (64, 192, 3), (256, 64, 1)])
+def test_fold_is_bit_exact(cuda, dt, cin, cout, k):
+    L = lib()
+    gen = torch.Generator().manual_seed(100 + cin + cout + k)
+    w_oihw = torch.randn(cout, cin, k, k, generator=gen).to(cuda)
+    gamma, beta, mean, var = _bn_params(cout, gen, cuda)
+    eps = 1e-5
+    scale, shift = torch.empty(cout, device=cuda), torch.empty(cout, device=cuda)
+    L.bn_eval_coeffs(cout, ptr(gamma), ptr(beta), ptr(mean), ptr(var), C.c_float(eps), ptr(scale), ptr(shift), stream())
+    d = _desc(2, 8, 8, cin, cout, k, 1)
+    ohwi = w_oihw.permute(0, 2, 3, 1).contiguous()
+    want = (ohwi * scale[:, None, None, None]).to(TDT[dt])
+    # the master once OHWI-contiguous (strides NULL), once as a channels_last OIHW view with its strides
+    cl = w_oihw.contiguous(memory_format=torch.channels_last)
+    for master, strides in ((ohwi, None), (cl, (C.c_int64 * 4)(*cl.stride())),
+                            (w_oihw, (C.c_int64 * 4)(*w_oihw.stride()))):
+        wf = torch.zeros(cout, k, k, cin, dtype=TDT[dt], device=cuda)
+        bias = torch.zeros(cout, device=cuda)
+        L.conv_fold_bn(C.byref(d), DT[dt], ptr(master), strides, ptr(gamma), ptr(beta), ptr(mean), ptr(var),
+                       C.c_float(eps), ptr(wf), ptr(bias), stream())
+        assert torch.equal(bias.view(torch.int32), shift.view(torch.int32))
+        bits = torch.int32 if dt == "fp32" else torch.int16
+        assert torch.equal(wf.view(bits), want.view(bits))
+
+
+# ---- 2. kernel parity ---------------------------------------------------------------------------------------
+# the smallest shapes that reach each failure mode: (n, h, w, cin, cout, k, stride)
+PARITY = [
+    (1, 6, 10, 64, 64, 1, 1),    # M = 60: below one tile
+    (3, 5, 7, 192, 64, 3, 1),    # ragged M, borders on every side, channels not a power of two
+    (2, 7, 9, 128, 192, 3, 2),   # odd frame, output 4 x 5
+    (2, 9, 7, 256, 128, 1, 2),   # the downsample kind
+    (2, 8, 8, 512, 512, 3, 1),   # the layer-4 shape that motivates the split
+]
+
+
+def _operands(cuda, dt, n, h, w, cin, cout, k, s, seed=0):
+    gen = torch.Generator().manual_seed(seed + 7 * cin + cout + k + s)
+    d = _desc(n, h, w, cin, cout, k, s)
+    x = torch.randn(n, h, w, cin, generator=gen).to(TDT[dt])  # NHWC, both signs
+    wf = (torch.randn(cout, k, k, cin, generator=gen) / (k * k * cin) ** 0.5).to(TDT[dt])
+    bias = torch.randn(cout, generator=gen) * 0.5
+    res = torch.randn(n, d.ho, d.wo, cout, generator=gen).to(TDT[dt])
+    y = F.conv2d(x.double().permute(0, 3, 1, 2), wf.double().permute(0, 3, 1, 2), stride=s, padding=d.pad)
+    y = y.permute(0, 2, 3, 1) + bias.double()  # NHWC fp64: conv + bias; negative in about half the places
+    return d, x.to(cuda), wf.to(cuda), bias.to(cuda), res.to(cuda), y, res.double()
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape", PARITY, ids=lambda s: "x".join(map(str, s)))
+def test_conv_infer_parity(cuda, dt, shape):
+    L = lib()
+    d, x, wf, bias, res, y, resd = _operands(cuda, dt, *shape)
+    assert (y < 0).float().mean() > 0.2  # ReLU matters
+    mx = L.dll.argus_conv_infer_max_splits(C.byref(d), DT[dt])
+    assert mx == shape[5] * shape[5] * shape[3] // (64 if dt == "bf16" else 32)
+    default = L.dll.argus_conv_infer_splits(C.byref(d), DT[dt])
+    assert 1 <= default <= mx
+    nbytes = max(L.dll.argus_conv_infer_workspace_bytes(C.byref(d), DT[dt], mx), 16)
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device=cuda)  # zeroed once for all the calls below
+    splits = sorted({min(s, mx) for s in (1, 2, 3, mx)}) + [0]  # 3 / the maximum: uneven / single-k-step slices
+    worst = 0.0
+    for use_res in (False, True):
+        for relu in (0, 1):
+            ref = y + resd if use_res else y
+            ref = ref.clamp_min(0) if relu else ref
+            bound = TOL[dt] * ref.abs().max().item()
+            for sp in splits:
+                out = torch.full(ref.shape, float("nan"), dtype=TDT[dt], device=cuda)
+                L.conv_infer(C.byref(d), DT[dt], ptr(x), ptr(wf), ptr(bias), ptr(res) if use_res else None, relu,
+                             ptr(out), sp, ptr(ws), ws.numel(), stream())
+                err = (out.double().cpu() - ref).abs().max().item()
+                worst = max(worst, err / bound)
+                assert err <= bound, f"{shape} {dt} res={use_res} relu={relu} splits={sp}: {err:.3e} > {bound:.3e}"
+    print(f"conv_infer {shape} {dt}: worst error / bound = {worst:.3f} (default splits {default}, max {mx})")
+
+
+# ---- 3. split determinism and workspace hygiene ------------------------------------------------------------
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+def test_split_is_deterministic_and_leaves_tickets_zero(cuda, dt):
+    L = lib()
+    d, x, wf, bias, res, y, resd = _operands(cuda, dt, 2, 8, 8, 512, 512, 3, 1)
+    wsb = [L.dll.argus_conv_infer_workspace_bytes(C.byref(d), DT[dt], s) for s in (2, 3, 4)]
+    slab = wsb[1] - wsb[0]
+    tickets = wsb[0] - 2 * slab  # bytes of ticket words at the start of the workspace
+    assert tickets > 0 and wsb[2] == tickets + 4 * slab
+    ws = torch.zeros(wsb[2], dtype=torch.uint8, device=cuda)  # zeroed once only
+    outs = []
+    for _ in range(2):
+        out = torch.empty(y.shape, dtype=TDT[dt], device=cuda)
+        L.conv_infer(C.byref(d), DT[dt], ptr(x), ptr(wf), ptr(bias), ptr(res), 1, ptr(out), 4, ptr(ws), ws.numel(),
+                     stream())
+        outs.append(out)
+        assert int(ws[:tickets].count_nonzero()) == 0  # every call leaves the tickets zero
+    assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
+    assert int(ws[tickets:].count_nonzero()) > 0  # the slabs were really used
+    # splits = 1 takes no ticket and touches no workspace: NULL is fine
+    out1 = torch.empty(y.shape, dtype=TDT[dt], device=cuda)
+    L.conv_infer(C.byref(d), DT[dt], ptr(x), ptr(wf), ptr(bias), ptr(res), 1, ptr(out1), 1, None, 0, stream())
+    ref = (y + resd).clamp_min(0)
+    assert (out1.double().cpu() - ref).abs().max().item() <= TOL[dt] * ref.abs().max().item()
+
+
+# ---- 4 / 5. the session ------------------------------------------------------------------------------------
+def _randomize_bn(model):
+    """Non-trivial BN parameters and running statistics, every layer from one seeded generator."""
+    g = torch.Generator().manual_seed(7)
+    for m in model.modules():
+        if isinstance(m, nn.BatchNorm2d):
+            c = m.num_features
+            m.weight.data = 0.5 + torch.rand(c, generator=g)
+            m.bias.data = 0.1 * torch.randn(c, generator=g)
+            m.running_mean.data = 0.1 * torch.randn(c, generator=g)
+            m.running_var.data = 0.5 + torch.rand(c, generator=g)
+
+
+@pytest.fixture(scope="module")
+def oracle():
+    from oracle.ncamera import build_reference_model
+
+    ref = build_reference_model(42)
+    _randomize_bn(ref)
+    return ref.eval()
+
+
+def _images(hw, seed=1234, batch=2):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, 256, (batch, 6, *hw), generator=g, dtype=torch.uint8)
+
+
+def _product(oracle, cuda, dtype):
+    from argus_amd.models import NCameraCNN
+
+    m = NCameraCNN(compute_dtype=dtype)
+    m.load_state_dict(oracle.state_dict())
+    return m.to(cuda).eval()
+
+
+@pytest.fixture(scope="module")
+def oracle_fp64(oracle):
+    """hw -> fp64 eval prediction of the oracle on the test images (computed once, shared, never modified)."""
+    import copy
+
+    ref64 = copy.deepcopy(oracle).double().eval()
+    out = {}
+    with torch.no_grad():
+        for hw in ((64, 64), (72, 104)):
+            out[hw] = ref64((_images(hw).float() / 255.0).double())
+    return out
+
+
+@pytest.mark.parametrize("hw", [(64, 64), (72, 104)], ids=["64x64", "72x104"])  # 72x104: ragged 9x13, 5x7, 3x4
+def test_session_matches_the_fp64_oracle(cuda, oracle, oracle_fp64, hw):
+    from argus_amd.infer import InferenceSession
+
+    x = (_images(hw).float() / 255.0).to(cuda)
+    ref = oracle_fp64[hw]
+    m32 = _product(oracle, cuda, "fp32")
+    d32 = (InferenceSession(m32, 2, hw)(x).double().cpu() - ref).abs().max().item()
+    m16 = _product(oracle, cuda, "bf16")
+    with torch.no_grad():
+        d_eval = (m16(x).double().cpu() - ref).abs().max().item()  # the existing bf16 eval path
+    d16 = (InferenceSession(m16, 2, hw)(x).double().cpu() - ref).abs().max().item()
+    print(f"session vs fp64 oracle {hw}: fp32 {d32:.3e}; bf16 session {d16:.3e}, bf16 model.eval() {d_eval:.3e}; "
+          f"max |pred| {ref.abs().max().item():.2f}")
+    assert d32 <= 1e-4
+    assert d16 <= 2 * d_eval
+
+
+class _Count:
+    """Counts the library calls a schedule makes (each is at least one kernel launch)."""
+
+    def __init__(self, L):
+        self._L, self.dll, self.n = L, L.dll, 0
+
+    def __getattr__(self, name):
+        fn = getattr(self._L, name)
+
+        def call(*a):
+            self.n += 1
+            return fn(*a)
+        return call
+
+
+def test_session_semantics(cuda, oracle):
+    from argus_amd.infer import InferenceSession
+    from argus_amd.utils import get_pose
+
+    hw = (64, 64)
+    model = _product(oracle, cuda, "fp32")
+    u8a, u8b = _images(hw, 1), _images(hw, 2)
+    # the division on the CPU, as the data pipeline does it (a device-side torch division by a scalar
+    # multiplies by the reciprocal: not the same bits)
+    xa, xb = (u8a.float() / 255.0).to(cuda), (u8b.float() / 255.0).to(cuda)
+    u8a = u8a.to(cuda)
+    before = {k: v.clone() for k, v in model.state_dict().items()}
+    sg, se = InferenceSession(model, 2, hw, graph=True), InferenceSession(model, 2, hw, graph=False)
+    ya = sg(xa)
+    assert ya.shape == (2, 6) and ya.dtype == torch.float32
+    assert torch.equal(ya, se(xa))  # replayed graph == eager launches
+    yb = sg(xb)
+    assert not torch.equal(ya, yb)
+    assert torch.equal(sg(xa), ya) and torch.equal(se(xb), yb)  # no stale state, no ticket residue
+    assert torch.equal(sg(u8a), ya) and torch.equal(se(u8a), ya)  # uint8 == its /255 float batch
+    assert ya.data_ptr() != sg(xa).data_ptr()  # a fresh tensor per call
+    # the session never writes the model, whatever its mode; it always uses the running statistics
+    model.train()
+    assert torch.equal(sg(xa), ya) and torch.equal(InferenceSession(model, 2, hw, graph=False)(xa), ya)
+    model.eval()
+    after = model.state_dict()
+    assert all(torch.equal(before[k], after[k]) for k in before) and "resnet.bn1.num_batches_tracked" in before
+    # a snapshot: model changes show only after refresh()
+    model.output_mlp[4].bias.data += 1
+    assert torch.equal(sg(xa), ya) and torch.equal(se(xa), ya)
+    sg.refresh()
+    se.refresh()
+    assert torch.equal(sg(xa), se(xa))
+    assert torch.allclose(sg(xa), ya + 1, rtol=0, atol=2e-6 * float(ya.abs().max() + 1))  # moved by that bias
+    assert torch.equal(sg.pose(xa), get_pose(xa, sg))
+    for bad in (xa[:1], xa[:, :3], xa[..., :32]):
+        with pytest.raises(ValueError, match="shape"):
+            sg(bad)
+    with pytest.raises(ValueError, match="float32 or uint8"):
+        sg(xa.double())
+    # launches: the eval engine's library calls per forward against the session's
+    eng = model._engine(cuda)
+    with torch.no_grad():
+        model(xa)
+        eng.L = cnt = _Count(eng.L)
+        model(xa)
+        eng.L = cnt._L
+    se.L = scnt = _Count(se.L)
+    se(xa)
+    se.L = scnt._L
+    assert scnt.n == se.launches_per_forward == sg.launches_per_forward
+    assert se.launches_per_forward < cnt.n, f"session {se.launches_per_forward} launches, eval engine {cnt.n}"
+    print(f"launches per forward: session {se.launches_per_forward}, eval engine {cnt.n}")
+    assert sg.activation_bytes > 0 and sg.weight_bytes > 0
