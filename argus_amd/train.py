@@ -88,6 +88,9 @@ class TrainConfig:
     # itself sets "high" (argus/train.py:26) and so trains on TF32 tensor cores; gfx950 has no TF32 / xf32
     # MFMA and exact fp32 stays the default here. Any other value is rejected.
     float32_matmul_precision: str = "highest"
+    # extension (--resident-dataset): decode the dataset once into device memory and build every batch there
+    # (argus_amd.resident: index gather + occluder arcs in one HIP launch) instead of the DataLoader workers
+    resident_dataset: bool = False
 
     def __post_init__(self) -> None:
         assert isinstance(self.save_dir, str)
@@ -180,6 +183,28 @@ def make_loaders(cfg: TrainConfig, train_ds, val_ds, rank: int = 0, world: int =
     return train_loader, val_loader, train_sampler, val_sampler
 
 
+def make_resident_loaders(cfg: TrainConfig, device: torch.device, rank: int = 0, world: int = 1):
+    """The ``--resident-dataset`` counterpart of ``make_loaders``: both splits decoded once into device memory
+    (``ResidentDataset``) and iterated by ``ResidentLoader``s with ``make_loaders``' sample order (shuffled
+    for training, ordered for validation, DistributedSampler sharding, seed 0 as its default) and arcs
+    seeded from ``cfg.random_seed``. Returns (train_loader, val_loader); ``set_epoch`` is the loader's."""
+    from argus_amd.resident import ResidentDataset, ResidentLoader
+
+    train_ds = ResidentDataset(cfg.dataset_config, cfg.augmentation_config, train=True, device=device,
+                               num_workers=cfg.num_workers)
+    val_ds = ResidentDataset(cfg.dataset_config, cfg.augmentation_config, train=False, device=device,
+                             num_workers=cfg.num_workers)
+    if world > 1:
+        kw = dict(rank=rank, world=world)
+    kw = dict(rank=rank, world=world, arc_seed=cfg.random_seed)
+    # DistributedSampler's default seed when sharded; a lone DataLoader shuffles from the global torch
+    # generator, here the order is seeded
+    train_loader = ResidentLoader(train_ds, cfg.batch_size, shuffle=True, seed=0 if world > 1 else cfg.random_seed,
+                                  **kw)
+    val_loader = ResidentLoader(val_ds, cfg.batch_size, shuffle=False, seed=0, **kw)
+    return train_loader, val_loader
+
+
 def initialize_training(cfg: TrainConfig, rank: int = 0, world: int = 1):
     """Seeds, device, datasets/loaders, model, fused trainer, LR schedule (train.py:122-255)."""
     from argus_amd.augment import DeviceAugmentation
@@ -196,11 +221,15 @@ def initialize_training(cfg: TrainConfig, rank: int = 0, world: int = 1):
         device = torch.device("cuda", torch.cuda.current_device())
     torch.cuda.set_device(device)
 
-    # uint8 batches: 4x less host->device traffic; the /255 of argus/data.py:214-215 runs on the device
-    train_ds = CameraCubePoseDataset(cfg.dataset_config, cfg_aug=cfg.augmentation_config, train=True, uint8=True,
-                                     device_augmentation=True)
-    val_ds = CameraCubePoseDataset(cfg.dataset_config, cfg_aug=cfg.augmentation_config, train=False, uint8=True)
-    train_loader, val_loader, train_sampler, val_sampler = make_loaders(cfg, train_ds, val_ds, rank, world)
+    if cfg.resident_dataset:  # decode once into device memory, batches built there (argus_amd.resident)
+        train_loader, val_loader = make_resident_loaders(cfg, device, rank, world)
+        train_sampler, val_sampler = train_loader, val_loader  # set_epoch is the loader's
+    else:
+        # uint8 batches: 4x less host->device traffic; the /255 of argus/data.py:214-215 runs on the device
+        train_ds = CameraCubePoseDataset(cfg.dataset_config, cfg_aug=cfg.augmentation_config, train=True, uint8=True,
+                                         device_augmentation=True)
+        val_ds = CameraCubePoseDataset(cfg.dataset_config, cfg_aug=cfg.augmentation_config, train=False, uint8=True)
+        train_loader, val_loader, train_sampler, val_sampler = make_loaders(cfg, train_ds, val_ds, rank, world)
     distributed = world > 1
 
     fp32_mode = "bf16x3" if cfg.float32_matmul_precision == "high" else "fp32"
@@ -242,6 +271,9 @@ def train(cfg: TrainConfig, rank: int = 0) -> str:
         if world > 1:
             dist.barrier()
             train_sampler.set_epoch(epoch)
+        if cfg.resident_dataset:  # the loaders' own set_epoch: sample order and arcs of this epoch
+            train_loader.set_epoch(epoch)
+            val_loader.set_epoch(epoch)
         model.train()
         epoch_losses = []
         for example in train_loader:

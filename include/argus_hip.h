@@ -514,6 +514,33 @@ size_t argus_augment_scratch_bytes(int64_t n_img, int h, int w);
 int argus_augment_photometric(int64_t n_img, int h, int w, const uint8_t* src, float* dst, const void* params,
                               float* scratch, argus_stream_t stream);
 
+/* ---- device-resident dataset (ABI 21, added without a version change: detect by symbol;
+ * csrc/resident.hip, argus_amd/resident.py) ---------------------------------------------------------
+ * argus_batch_gather_occlude: one launch builds a batch from cropped uint8 frames kept in device memory: out[b] = store[index[b]]
+ * with every pixel covered by one of its camera image's n_arcs occluder arcs set to 0 in all three
+ * channels. store: (n_samples, 3*n_cams, h, w) planar uint8; index: batch int64 entries in device
+ * memory - an entry outside [0, n_samples) is CLAMPED to that range (the launch cannot report it);
+ * arcs: batch*n_cams*n_arcs records of argus_arc_record_bytes() bytes in device memory, image
+ * (b, cam)'s records at (b*n_cams + cam)*n_arcs (n_arcs may be 0: arcs is then ignored); a record is
+ * 12 int32 {x0, y0, x1, y1, width, mode, sx, sy, ex, ey, 0, 0}: the box of ImageDraw.arc in
+ * SOURCE-frame pixels (the crop's origin there is crop_y0, crop_x0), mode 0 nothing / 1 full ellipse
+ * / 2 span <= 180 degrees / 3 span > 180, (sx, sy) and (ex, ey) = round(2^20 (cos, sin)) of the start
+ * and end angle (clockwise from 3 o'clock, y down). The covered set is the integer closed form stated
+ * in resident.hip; every coordinate lies in [0, 8192) (a record outside covers nothing; a crop outside:
+ * ARGUS_ERR_SHAPE). out: (batch, 3*n_cams, h, w), written once per byte (no atomics: deterministic,
+ * independent of the arc order); must not overlap store. Allocates nothing; capturable. */
+size_t argus_arc_record_bytes(void);
+/* Host only: the np.random draws of the reference's draw_spaghetti (argus/utils.py:252-275) for n_arcs arcs
+ * on a src_h x src_w frame, continued from a numpy RandomState's MT19937 state (mt_key: 624 words,
+ * *mt_pos: its position; both updated, so the RandomState can go on from them). Per arc, in order:
+ * randint(0, W), randint(0, H), randint(x0, W), randint(y0, H), randint(0, 360) twice,
+ * int(uniform(width_lo, width_hi)). params: n_arcs x 7 int32 {x0, y0, x1, y1, a0, a1, width}. */
+int argus_sample_arc_params(uint32_t* mt_key, int* mt_pos, int64_t n_arcs, int src_h, int src_w, double width_lo,
+                            double width_hi, int32_t* params);
+int argus_batch_gather_occlude(int64_t batch, int n_cams, int h, int w, const uint8_t* store, int64_t n_samples,
+                               const int64_t* index, const void* arcs, int n_arcs, int crop_y0, int crop_x0,
+                               uint8_t* out, argus_stream_t stream);
+
 /* ---- optimizer step (clip_grad_norm_ + Adam, argus/train.py:232,317-320) --------------------- */
 size_t argus_sumsq_workspace_bytes(int64_t count);
 /* out[0] = sqrt(sum x^2) (fp32, deterministic two-level reduction). */
