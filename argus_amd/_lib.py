@@ -120,6 +120,7 @@ SIGNATURES = {
     "argus_conv_wgrad_workspace_bytes": (_SZ, [_DESC, _I]),
     "argus_conv_wgrad": (_I, [_DESC, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "argus_conv_wgrad_apply": (_I, [_DESC, _I, _P, _P, C.POINTER(BnBwdPrologue), _P, _P, _SZ, _P]),
+    "argus_conv_stem_dgrad": (_I, [_DESC, _I, _P, _P, C.POINTER(BnBwdPrologue), _P, _P]),
     "argus_conv_dgrad_wgrad_ok": (_I, [_DESC, _I]),
     "argus_conv_dgrad_wgrad_workspace_bytes": (_SZ, [_DESC, _I]),
     "argus_conv_dgrad_wgrad_bn_rows": (_I, [_DESC, _I]),

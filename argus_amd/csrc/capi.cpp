@@ -196,6 +196,12 @@ int argus_conv_wgrad_apply(const argus_conv_desc* d, int dtype, const void* x, c
   return conv_wgrad_apply(*d, dtype, x, dm, *ap, dw, ws, ws_bytes, (hipStream_t)stream);
 }
 
+int argus_conv_stem_dgrad(const argus_conv_desc* d, int dtype, const void* dy, const void* w_fwd,
+                          const argus_bn_bwd_prologue* ap, float* dx_nchw, argus_stream_t stream) {
+  if (!d || !dy || !w_fwd || !dx_nchw) { set_error("conv_stem_dgrad: null argument"); return ARGUS_ERR_ARG; }
+  return conv_stem_dgrad(*d, dtype, dy, w_fwd, ap, dx_nchw, (hipStream_t)stream);
+}
+
 int argus_conv_dgrad_wgrad_ok(const argus_conv_desc* d, int dtype) {
   return d && !conv_check_desc(*d) && conv_dgw_ok(*d, dtype) ? 1 : 0;
 }

@@ -100,6 +100,9 @@ int conv_dgrad_bn(const argus_conv_desc& d, int dtype, const void* dy, const voi
 size_t conv_wgrad_ws(const argus_conv_desc& d, int dtype);
 int conv_wgrad_apply(const argus_conv_desc& d, int dtype, const void* x, const void* dm,
                      const argus_bn_bwd_prologue& ap, float* dw, void* ws, size_t ws_bytes, hipStream_t st);
+// the stem's data gradient (stem_dgrad.hip): dx (n, 3, h, w) fp32 planar from dy, or from dm through `ap`
+int conv_stem_dgrad(const argus_conv_desc& d, int dtype, const void* dy, const void* w_fwd,
+                    const argus_bn_bwd_prologue* ap, float* dx, hipStream_t st);
 int conv_wgrad(const argus_conv_desc& d, int dtype, const void* x, const float* sc,
                const float* sh, const void* dy, float* dw, void* ws, size_t ws_bytes,
                hipStream_t st);

@@ -575,8 +575,13 @@ class ResNetEngine:
         return self.pred
 
     # ------------------------------------------------------------------ backward
-    def backward(self, dpred: torch.Tensor, P: dict, G: dict, on_ready=None) -> None:
+    def backward(self, dpred: torch.Tensor, P: dict, G: dict, on_ready=None, dx: torch.Tensor | None = None) -> None:
         """Write every parameter gradient into G[name] (fp32; conv weights OHWI-contiguous).
+
+        ``dx`` (optional): an fp32 (B, 3*n_cams, H, W) contiguous tensor on the engine's device that receives
+        the gradient of the images (the stem's data gradient, argus_conv_stem_dgrad: one more launch on the
+        main stream at the end of the backward). With None the backward issues exactly the launches it
+        issues without this argument.
 
         ``on_ready(name, comm)`` (optional) is called, in stream order, as soon as the gradients of
         parameter ``name`` and of every parameter registered after it have been issued: after the head
@@ -589,6 +594,11 @@ class ResNetEngine:
             raise RuntimeError("backward without a saved train-mode forward")
         L, dt, s = self.L, self.dt, stream()
         B = self.shape[0]
+        if dx is not None and (dx.dtype != torch.float32 or dx.device != self.device or not dx.is_contiguous()
+                               or tuple(dx.shape) != (B, 3 * self.n_cams, *self.shape[1:])):
+            raise ValueError(f"dx must be a contiguous fp32 {(B, 3 * self.n_cams, *self.shape[1:])} tensor on "
+                             f"{self.device}")
+        dx_img = dx  # (`dx` names each block's input gradient below)
         N = self.N
         D = self.n_cams * self.rdim
         dpred = dpred.contiguous().float()
@@ -824,13 +834,28 @@ class ResNetEngine:
             for cvt, fnt in self._tail:  # after the stem's: they share its workspace (stream order)
                 self._launch(cvt, 2, fnt)
             self._tail.clear()
+            if dx_img is not None:  # reads dm0, y0, cf and the stem's w_fwd only: the same apply, staged from dm0
+                self._stem_dgrad(dz0, ap, dx_img)
         else:
             L.maxpool_bwd(dt, N, H1, W1, 64, ptr(dh), ptr(self.amax), ptr(dz0), s)
             self._bn_bwd(P, G, "resnet.bn1", N * H1 * W1, 64, dz0, 2, None, self.y0, dy0, None)
             self._wgrad("resnet.conv1", self.x0, None, dy0, G)
+            if dx_img is not None:  # the materialised dy0 (the side stream's weight gradient only reads it)
+                self._stem_dgrad(dy0, None, dx_img)
         self._join()
         if on_ready is not None:
             on_ready("resnet.conv1.weight", self._comm)
+
+    def _stem_dgrad(self, dy, ap, dx) -> None:
+        """dx (N, 3, H, W) fp32 = the stem conv's data gradient of ``dy`` (of dm0 through the apply ``ap``),
+        on the main stream before the final join: stream order protects dm0 / y0 / dy0 from the next
+        forward."""
+        cv = self.convs["resnet.conv1"]
+        self._launch(cv, 1, lambda: self.L.conv_stem_dgrad(C.byref(cv.desc), self.dt, ptr(dy), ptr(cv.wf),
+                                                            C.byref(ap) if ap is not None else None, ptr(dx),
+                                                            stream()))
+        if self.debug is not None:
+            self.debug["bwd.dx"] = dx.clone()
 
     def _y3_free(self, idx: int) -> bool:
         """Block ``idx``'s bn3 input y3 is never stored: its forward tail is fused, the next block's

@@ -83,11 +83,15 @@ class _NetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, model, *params):
+        if ctx.needs_input_grad[0] and x.dtype != torch.float32:
+            raise RuntimeError(f"argus_amd: the image gradient is produced for fp32 images only, got {x.dtype} "
+                               "images that require grad (convert them with .float() first)")
         engine = model._engine(x.device)
         P, Bf = model._maps()
         pred = engine.forward(x, P, Bf, model.training).clone()
         engine.fwd_id = getattr(engine, "fwd_id", 0) + 1
         ctx.engine, ctx.model, ctx.fwd_id = engine, model, engine.fwd_id
+        ctx.x_shape = tuple(x.shape)
         return pred
 
     @staticmethod
@@ -103,12 +107,17 @@ class _NetFn(torch.autograd.Function):
                 G[name] = torch.empty(conv_grad_shape(p.shape), dtype=torch.float32, device=p.device)
             else:
                 G[name] = torch.empty_like(p)
-        engine.backward(dpred, P, G)
+        # d loss / d images (the stem's data gradient, argus_conv_stem_dgrad) only when the caller asked for
+        # it; no double backward: the returned gradient carries no graph
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dpred.device)
+        engine.backward(dpred, P, G, dx=dx)
         grads = []
         for name, p in model.named_parameters():
             g = G[name]
             grads.append(g.permute(0, 3, 1, 2) if g.dim() == 4 else g)
-        return (None, None, *grads)
+        return (dx, None, *grads)
 
 
 def strip_checkpoint_prefixes(state_dict):

@@ -136,11 +136,20 @@ class FusedTrainer:
         # all-reduce after the backward's own work - the collective tail the overlap did not hide
         self.tail_events: list | None = None
 
-    def step(self, images: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
-        """One optimisation step on a device-resident batch; returns the per-sample losses (B,)."""
+    def step(self, images: torch.Tensor, targets: torch.Tensor,
+             image_grad: torch.Tensor | None = None) -> torch.Tensor:
+        """One optimisation step on a device-resident batch; returns the per-sample losses (B,).
+
+        ``image_grad`` (optional): a contiguous fp32 tensor of the images' shape on their device; d(mean
+        loss)/d(images) of this step is written into it by the same backward that feeds Adam (the "free"
+        adversarial-training pattern). Under data parallelism it is this rank's gradient of its local mean
+        loss: nothing is all-reduced."""
         model = self.model
         if not model.training:
             raise RuntimeError("FusedTrainer.step needs model.train()")
+        if image_grad is not None and (image_grad.dtype != torch.float32 or image_grad.shape != images.shape
+                                       or image_grad.device != images.device or not image_grad.is_contiguous()):
+            raise ValueError("image_grad must be a contiguous fp32 tensor of the images' shape on their device")
         L = lib()
         s = stream()
         B = images.shape[0]
@@ -154,7 +163,7 @@ class FusedTrainer:
         L.se3_loss(B, ptr(pred), ptr(targets), ptr(self._loss), ptr(self._dpred), C.c_float(1.0 / B), s)
         if self.bucketer is not None:
             self.bucketer.start()
-            eng.backward(self._dpred, P, self.flat.G, on_ready=self.bucketer.ready)
+            eng.backward(self._dpred, P, self.flat.G, on_ready=self.bucketer.ready, dx=image_grad)
             t0 = t1 = None
             if self.tail_events is not None:  # main stream: end of its backward work -> collectives done
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -164,7 +173,7 @@ class FusedTrainer:
                 t1.record()
                 self.tail_events.append((t0, t1))
         else:
-            eng.backward(self._dpred, P, self.flat.G)
+            eng.backward(self._dpred, P, self.flat.G, dx=image_grad)
         self.step_count += 1
         b1, b2 = self.betas
         t = self.step_count

@@ -2,6 +2,7 @@
 
     python -m argus_amd.timing [--trials 100] [--batch 2] [--hw 256 256] [--dtype fp32|bf16x3|bf16]
                                [--eval] [--no-graph] [--frozen]
+    python -m argus_amd.timing --input-grad [--out profiles/input_grad.txt]
 
 Reference semantics (scripts/timing.py:10-48): ``NCameraCNN(n_cams=2)`` in fp32 on the GPU, left in
 its default (train) mode — BatchNorm uses batch statistics — a fresh ``torch.rand((2, 6, 256, 256))``
@@ -15,6 +16,9 @@ copied into the graph's static input buffer; ``--no-graph`` times eager launches
 
 ``--frozen`` times an ``argus_amd.infer.InferenceSession`` built from the model in eval mode instead (BN
 folded into the conv weights, one launch per conv, its own captured graph): the deployment path.
+
+``--input-grad`` measures the image gradient instead (``input_grad_table``): the stem data-gradient kernel
+alone against MIOpen's, and the train step with and without ``image_grad``.
 
 One deliberate difference: the reference prints ``np.mean(runtime)`` — the last trial only
 (scripts/timing.py:48); this prints the mean (and median, min) over all timed trials.
@@ -88,8 +92,124 @@ def forward_latency(trials: int = 100, batch: int = 2, hw=(256, 256), dtype: str
     return r
 
 
+def _event_ms(fn, reps: int) -> float:
+    """Milliseconds per call of ``fn`` over ``reps`` back-to-back calls between two device events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def input_grad_table(rounds: int = 3, samples: int = 20, device: str = "cuda") -> list:
+    """The image-gradient measurement (``--input-grad``), as the lines of profiles/input_grad.txt.
+
+    (a) argus_conv_stem_dgrad alone at N=128 and N=2, 256x256, bf16 and fp32: with the apply prologue (the
+        call the fused schedule makes) and on a materialised dy, against ``torch.nn.grad.conv2d_input``
+        (MIOpen) on the same materialised dy and weights, given as the NHWC memory the kernel reads
+        (channels_last) and as NCHW. The yardstick does less: no apply, no planar fp32 output.
+    (b) ``FusedTrainer.step`` at B=64, bf16, 256x256, with and without ``image_grad``.
+    Device events, the arms interleaved, ``rounds`` rounds; every cell is the median over ``samples`` samples
+    (kernel arms: 10 back-to-back calls a sample)."""
+    import ctypes as C
+
+    from argus_amd._lib import BF16, F32, BnBwdPrologue, ConvDesc, lib, ptr, stream
+    from argus_amd.step import FusedTrainer
+
+    L = lib()
+    lines = ["# Image gradient (argus_conv_stem_dgrad), one MI355X, 256x256, python -m argus_amd.timing --input-grad",
+             "# device events, arms interleaved, %d rounds, median / min over %d samples a cell; ms" % (rounds, samples),
+             "# (a) kernel alone, 10 back-to-back calls a sample. apply = dy formed from dm, y, ca/cb/cc while staging",
+             "#     (what the fused backward launches); plain = a materialised dy; miopen_* = torch.nn.grad.conv2d_input",
+             "#     on that materialised dy (no apply; output in the compute dtype, not planar fp32), dy as the",
+             "#     kernel's NHWC memory (channels_last) or NCHW-contiguous. N=2 operands stay cache-resident.",
+             "# part dtype     N arm          round   median      min"]
+    med = {}
+    for dtype, tdt, dt in (("bf16", torch.bfloat16, BF16), ("fp32", torch.float32, F32)):
+        for N in (128, 2):
+            torch.manual_seed(0)
+            d = ConvDesc(N, 256, 256, 3, 64, 7, 7, 2, 3, 128, 128, 1)
+            w = torch.randn(64, 7, 7, 3, device=device) * 0.1
+            wf = torch.empty(64, 256, dtype=tdt, device=device)
+            L.conv_weight_prep(C.byref(d), dt, ptr(w), None, ptr(wf), None, stream())
+            dm = torch.randn(N, 128, 128, 64, device=device).to(tdt)
+            y = torch.randn(N, 128, 128, 64, device=device).to(tdt)
+            ca, cb, cc = (torch.randn(64, device=device) * 0.5 for _ in range(3))
+            dy = torch.empty_like(dm)
+            L.bn_bwd_apply(dt, N * 128 * 128, 64, ptr(dm), 0, None, ptr(y), None, None, ptr(ca), ptr(cb), ptr(cc),
+                           ptr(dy), None, None, None, None, None, None, stream())
+            dx = torch.empty(N, 3, 256, 256, device=device)
+            pro = BnBwdPrologue(ptr(y), ptr(ca), ptr(cb), ptr(cc), None)
+            w_oihw = w.permute(0, 3, 1, 2).contiguous().to(tdt)
+            dy_cl = dy.permute(0, 3, 1, 2)  # (N, 64, 128, 128) over the NHWC memory
+            dy_nchw = dy_cl.contiguous()
+            arms = {
+                "apply": lambda: L.conv_stem_dgrad(C.byref(d), dt, ptr(dm), ptr(wf), C.byref(pro), ptr(dx), stream()),
+                "plain": lambda: L.conv_stem_dgrad(C.byref(d), dt, ptr(dy), ptr(wf), None, ptr(dx), stream()),
+                "miopen_nhwc": lambda: torch.nn.grad.conv2d_input((N, 3, 256, 256), w_oihw, dy_cl, stride=2, padding=3),
+                "miopen_nchw": lambda: torch.nn.grad.conv2d_input((N, 3, 256, 256), w_oihw, dy_nchw, stride=2,
+                                                                  padding=3),
+            }
+            for name in list(arms):  # warm-up (code objects, MIOpen's solver choice); an arm that fails is reported
+                try:
+                    _event_ms(arms[name], 3)
+                except Exception as e:  # noqa: BLE001
+                    lines.append(f"a    {dtype:5s} {N:5d} {name:12s} failed: {type(e).__name__}: {str(e)[:80]}")
+                    del arms[name]
+            for rnd in range(1, rounds + 1):
+                for name, fn in arms.items():
+                    ts = [_event_ms(fn, 10) for _ in range(samples)]
+                    m = statistics.median(ts)
+                    med.setdefault((dtype, N, name), []).append(m)
+                    lines.append(f"a    {dtype:5s} {N:5d} {name:12s} {rnd:5d} {m:8.4f} {min(ts):8.4f}")
+            del dm, y, dy, dx, dy_nchw
+            torch.cuda.empty_cache()
+    lines.append("# (b) FusedTrainer.step, B=64, bf16: one step a sample")
+    trainers = {}
+    x = torch.rand(64, 6, 256, 256, device=device)
+    from oracle import se3
+
+    T = se3.random_targets(64, generator=torch.Generator().manual_seed(0)).float().to(device)
+    buf = torch.empty_like(x)
+    for name in ("step", "step+image_grad"):
+        torch.manual_seed(0)
+        model = NCameraCNN(NCameraCNNConfig(n_cams=2), compute_dtype="bf16").to(device).train()
+        trainers[name] = FusedTrainer(model, lr=1e-5, max_grad_norm=1.0)
+    steps = {"step": lambda: trainers["step"].step(x, T),
+             "step+image_grad": lambda: trainers["step+image_grad"].step(x, T, image_grad=buf)}
+    for fn in steps.values():
+        _event_ms(fn, 3)
+    for rnd in range(1, rounds + 1):
+        for name, fn in steps.items():
+            ts = [_event_ms(fn, 1) for _ in range(samples)]
+            m = statistics.median(ts)
+            med.setdefault(("bf16", 64, name), []).append(m)
+            lines.append(f"b    bf16  {64:5d} {name:15s} {rnd:2d} {m:8.4f} {min(ts):8.4f}")
+    lines += ["", "# summary: median of the round medians"]
+    mm = {k: statistics.median(v) for k, v in med.items()}
+    for dtype in ("bf16", "fp32"):
+        for N in (128, 2):
+            ours = mm.get((dtype, N, "apply"))
+            yard = [v for k, v in mm.items() if k[:2] == (dtype, N) and k[2].startswith("miopen")]
+            if ours is None or not yard:
+                continue
+            best = min(yard)
+            lines.append(f"{dtype} N={N:<3d} kernel+apply {ours:8.4f} | plain {mm[(dtype, N, 'plain')]:8.4f} | "
+                         f"miopen best {best:8.4f} | ours/miopen {ours / best:5.2f}x "
+                         f"({'faster' if ours < best else 'slower'} than the yardstick)")
+    extra = mm[("bf16", 64, "step+image_grad")] - mm[("bf16", 64, "step")]
+    lines.append(f"step B=64 bf16: {mm[('bf16', 64, 'step')]:8.4f} -> {mm[('bf16', 64, 'step+image_grad')]:8.4f} with "
+                 f"image_grad: +{extra:.4f} ms; the kernel alone at N=128 bf16 (apply): {mm[('bf16', 128, 'apply')]:.4f} ms")
+    return lines
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--input-grad", action="store_true",
+                    help="measure the image-gradient kernel and the step with image_grad (writes --out)")
+    ap.add_argument("--out", default="profiles/input_grad.txt", help="where --input-grad writes its table")
     ap.add_argument("--trials", type=int, default=100)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--hw", type=int, nargs=2, default=(256, 256))
@@ -99,6 +219,12 @@ def main() -> None:
     ap.add_argument("--frozen", action="store_true",
                     help="time an InferenceSession of the eval-mode model (fp32 / bf16)")
     a = ap.parse_args()
+    if a.input_grad:
+        lines = input_grad_table()
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        print("\n".join(lines))
+        return
     r = forward_latency(a.trials, a.batch, tuple(a.hw), a.dtype, not a.eval, not a.no_graph, frozen=a.frozen)
     print(f"Forward pass took {r['mean_s']} seconds on average.")
     print(json.dumps(r))

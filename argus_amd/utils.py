@@ -5,6 +5,9 @@
 - ``get_pose(images, model)`` (utils.py:179-189): ``se3(model(images)).Exp()`` -> (B, 7), with the
   Exp on the HIP kernel (argus_se3_exp).
 - ``time_torch_fn`` (utils.py:153-171): HIP-event timing of a callable.
+- ``image_gradient(model, images, target)``: d(mean loss)/d(images) through autograd (the stem's data
+  gradient kernel, argus_conv_stem_dgrad); no counterpart function in the reference, whose ``nn.Module``
+  gives the same gradient under stock autograd.
 - ``draw_spaghetti`` (utils.py:252-275): random black PIL arcs ("spaghetti" occluders) drawn on a
   camera image; the same ``np.random`` draws in the same order as the reference, so a seeded worker
   draws the same arcs.
@@ -63,6 +66,25 @@ def get_pose(images: torch.Tensor, model: torch.nn.Module) -> torch.Tensor:
     returning (B, 6) se(3) vectors: an ``NCameraCNN``, or an ``argus_amd.infer.InferenceSession`` of one (the
     frozen deployment path; ``session.pose(images)`` is the same call)."""
     return se3_exp(model(images))
+
+
+def image_gradient(model: torch.nn.Module, images: torch.Tensor, target: torch.Tensor) -> tuple:
+    """(losses (B,), grad) with grad = d(mean SE(3) loss)/d(images), fp32 of ``images``' shape: pixel
+    saliency of the predicted pose (reduce it with e.g. ``grad.abs().amax(1)``), or the direction of an
+    FGSM perturbation.
+
+    ``images`` is a (B, 3*n_cams, H, W) floating tensor on the model's device (converted to fp32), ``target``
+    (B, 7) poses as the loss takes them. A thin helper over autograd:
+
+    - Train-mode (batch) statistics only: the engine has no eval-mode backward, so ``model`` must be in
+      ``train()`` mode, and the forward updates the BN running statistics as any train-mode forward does.
+    - Parameter ``.grad``s are left untouched (``torch.autograd.grad`` with the images as the only input)."""
+    from argus_amd.losses import geometric_loss_fn
+
+    x = images.detach().float().requires_grad_(True)
+    losses = geometric_loss_fn(model(x), target)
+    (grad,) = torch.autograd.grad(losses.mean(), x)
+    return losses.detach(), grad
 
 
 def time_torch_fn(fn: Callable[[], torch.Tensor]) -> tuple:

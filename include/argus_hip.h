@@ -347,6 +347,19 @@ int argus_conv_wgrad(const argus_conv_desc* d, int dtype, const void* x, const f
 int argus_conv_wgrad_apply(const argus_conv_desc* d, int dtype, const void* x, const void* dm,
                            const argus_bn_bwd_prologue* ap, float* dw, void* workspace,
                            size_t workspace_bytes, argus_stream_t stream);
+/* Data gradient of the stem convolution: autograd's grad_input of resnet.conv1 (torchvision conv1, 7x7
+ * stride 2 pad 3, 3 -> 64 channels; argus/models.py:43) under loss.backward() (argus/train.py:316) when
+ * the images require grad, i.e. F.conv2d's gradient with respect to its input. `d` is a stem descriptor
+ * (stem = 1, c = 3, k = 64); dtype ARGUS_F32 or ARGUS_BF16 (anything else: ARGUS_ERR_ARG). `dy` is
+ * (n, ho, wo, 64) NHWC in dtype; with `ap` it holds dm and the kernel consumes ca*dm + cb*y + cc per
+ * channel, formed while staging with argus_bn_bwd_apply's formula and rounding (bf16: rounded to bf16
+ * before the product; ap->dy_out is ignored, nothing is materialised). `w_fwd` is the stem's compute copy
+ * [64][8][8][4] that argus_conv_weight_prep writes. `dx_nchw` is fp32 (n, 3, h, w) planar (folded over the
+ * cameras: the (B, 3*n_cams, H, W) images layout); every element is written, accumulation is fp32 (fp32
+ * mode: the exact fp32 MFMA), each output sums its own 9..16 taps in a fixed order: bit-reproducible, no
+ * atomics. Allocates nothing, synchronises nothing, capturable. */
+int argus_conv_stem_dgrad(const argus_conv_desc* d, int dtype, const void* dy, const void* w_fwd,
+                          const argus_bn_bwd_prologue* ap, float* dx_nchw, argus_stream_t stream);
 /* Data and weight gradient of one 1x1 stride-1 conv in one pass over its output gradient (torch's
  * convolution backward with output_mask (grad_input, grad_weight) for Bottleneck.conv3 of ResNet-50
  * layer 1 and of the first block's downsample, reached from loss.backward() at argus/train.py:316;
