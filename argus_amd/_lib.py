@@ -18,6 +18,7 @@ import torch  # noqa: F401  (must precede the CDLL, see module docstring)
 LIB_PATH = Path(os.environ.get("ARGUS_HIP_LIB", Path(__file__).resolve().parent / "libargus_hip.so"))
 
 F32, BF16, FP8 = 0, 1, 2
+F16 = 3  # frozen inference only (InferenceSession(compute_dtype="fp16")): include/argus_hip.h
 ABI_VERSION = 21
 
 

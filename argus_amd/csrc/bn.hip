@@ -549,7 +549,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(int n, int H, int W, i
         const int iw = 2 * ow - 1 + t;
         if ((unsigned)iw >= (unsigned)W) continue;
         float v[E];
-        unpack(ld16(yb + (ih * W + iw) * C), v);
+        ChunkCvt<T>::unpack(ld16(yb + (ih * W + iw) * C), v);
 #pragma unroll
         for (int j = 0; j < E; ++j) {
           const float z = fmaxf(fmaf(v[j], s[j], h[j]), 0.f);
@@ -557,7 +557,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(int n, int H, int W, i
         }
       }
     }
-    st16(out + (size_t)pix * C + c0, pack(best));
+    st16(out + (size_t)pix * C + c0, ChunkCvt<T>::pack(best));
     if constexpr (E == 8) {
       const uint2 a = {idx[0] | idx[1] << 8 | idx[2] << 16 | idx[3] << 24, idx[4] | idx[5] << 8 | idx[6] << 16 | idx[7] << 24};
       *reinterpret_cast<AV*>(amax + (size_t)pix * C + c0) = a;
@@ -799,6 +799,7 @@ int argus_bn_eval_coeffs(int C, const float* gamma, const float* beta, const flo
 int argus_bn_apply(int dtype, int64_t pixels, int C, const void* y, const float* scale, const float* shift,
                    const void* res, const float* rsc, const float* rsh, int relu, void* out, uint8_t* mask_out,
                    argus_stream_t stream) {
+  if (f16_unserved(dtype, "bn_apply")) return ARGUS_ERR_ARG;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
   if (C % E || pixels <= 0 || !y || !scale || !shift || !out || ((rsc == nullptr) != (rsh == nullptr)) ||
       (rsc && !res)) {
@@ -853,6 +854,7 @@ int argus_bn_bwd_reduce(int dtype, int64_t pixels, int C, const void* dz, int mo
                         const void* y, const float* scale, const float* shift, const float* mean,
                         const float* invstd, float* part, const void* y2, const float* mean2, const float* invstd2,
                         float* part2, argus_stream_t stream) {
+  if (f16_unserved(dtype, "bn_bwd_reduce")) return ARGUS_ERR_ARG;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
   if (C % E || pixels <= 0) { set_error("bn_bwd_reduce: bad shape"); return ARGUS_ERR_SHAPE; }
   const bool dual = y2 != nullptr;
@@ -910,6 +912,7 @@ int argus_bn_bwd_apply(int dtype, int64_t pixels, int C, const void* dz, int mod
                        const float* scale, const float* shift, const float* ca, const float* cb, const float* cc,
                        void* dy, void* dm_out, const void* y2, const float* ca2, const float* cb2, const float* cc2,
                        void* dy2, argus_stream_t stream) {
+  if (f16_unserved(dtype, "bn_bwd_apply")) return ARGUS_ERR_ARG;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
   const bool dual = y2 != nullptr;
   if (C % E || pixels <= 0 || !dz || !y || !ca || !cb || !cc || !dy || mode < 0 || mode > 3 ||
@@ -965,7 +968,7 @@ int argus_bn_bwd_apply_x8(int64_t pixels, int C, const void* dm, const void* y, 
 
 int argus_maxpool_fwd(int dtype, int n, int h, int w, int c, const void* y, const float* scale, const float* shift,
                       void* out, uint8_t* amax, argus_stream_t stream) {
-  const int E = dtype == ARGUS_BF16 ? 8 : 4;
+  const int E = dtype == ARGUS_BF16 || dtype == ARGUS_F16 ? 8 : 4;
   if (c % E) { set_error("maxpool_fwd: bad channels"); return ARGUS_ERR_SHAPE; }
   if ((int64_t)n * h * w * c >= (1LL << 31)) { set_error("maxpool_fwd: tensor exceeds 2^31 elements"); return ARGUS_ERR_SHAPE; }
   const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
@@ -974,6 +977,9 @@ int argus_maxpool_fwd(int dtype, int n, int h, int w, int c, const void* y, cons
   if (dtype == ARGUS_BF16)
     hipLaunchKernelGGL(maxpool_fwd_kernel<bf16>, dim3(grid_for(work)), dim3(256), 0, st, n, h, w, c, ho, wo,
                        (const bf16*)y, scale, shift, (bf16*)out, amax);
+  else if (dtype == ARGUS_F16)
+    hipLaunchKernelGGL(maxpool_fwd_kernel<f16>, dim3(grid_for(work)), dim3(256), 0, st, n, h, w, c, ho, wo,
+                       (const f16*)y, scale, shift, (f16*)out, amax);
   else
     hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid_for(work)), dim3(256), 0, st, n, h, w, c, ho, wo,
                        (const float*)y, scale, shift, (float*)out, amax);
@@ -982,11 +988,13 @@ int argus_maxpool_fwd(int dtype, int n, int h, int w, int c, const void* y, cons
 
 int argus_maxpool_bwd(int dtype, int n, int h, int w, int c, const void* dout, const uint8_t* amax, void* dz,
                       argus_stream_t stream) {
+  if (f16_unserved(dtype, "maxpool_bwd")) return ARGUS_ERR_ARG;
   return argus_maxpool_bwd_bn(dtype, n, h, w, c, dout, amax, dz, nullptr, nullptr, nullptr, nullptr, nullptr,
                               nullptr, stream);
 }
 
 int argus_maxpool_bwd_bn_rows(int dtype, int n, int h, int w, int c) {
+  if (f16_unserved(dtype, "maxpool_bwd_bn_rows")) return -1;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
   return c % E ? -1 : grid_for((int64_t)n * h * w * (c / E), kMaxpoolBwdBlocks);
 }
@@ -994,6 +1002,7 @@ int argus_maxpool_bwd_bn_rows(int dtype, int n, int h, int w, int c) {
 int argus_maxpool_bwd_bn(int dtype, int n, int h, int w, int c, const void* dout, const uint8_t* amax, void* dm,
                          const void* y, const float* scale, const float* shift, const float* mean,
                          const float* invstd, float* part, argus_stream_t stream) {
+  if (f16_unserved(dtype, "maxpool_bwd_bn")) return ARGUS_ERR_ARG;
   return argus_maxpool_bwd_bn_fin(dtype, n, h, w, c, dout, amax, dm, y, scale, shift, mean, invstd, part, nullptr,
                                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
@@ -1002,6 +1011,7 @@ int argus_maxpool_bwd_bn_fin(int dtype, int n, int h, int w, int c, const void* 
                              const void* y, const float* scale, const float* shift, const float* mean,
                              const float* invstd, float* part, const float* gamma, float* dgamma, float* dbeta,
                              float* ca, float* cb, float* cc, void* workspace, argus_stream_t stream) {
+  if (f16_unserved(dtype, "maxpool_bwd_bn_fin")) return ARGUS_ERR_ARG;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
   if (c % E || 256 % (c / E) || c > 256) { set_error("maxpool_bwd: bad channels"); return ARGUS_ERR_SHAPE; }
   if ((int64_t)n * h * w * c >= (1LL << 31)) { set_error("maxpool_bwd: tensor exceeds 2^31 elements"); return ARGUS_ERR_SHAPE; }
@@ -1045,12 +1055,15 @@ int argus_avgpool_fwd(int dtype, int n, int hw, int c, const void* x, float* fea
   const int blocks = (int)((work + 255) / 256);
   if (dtype == ARGUS_BF16)
     hipLaunchKernelGGL(avgpool_fwd_kernel<bf16>, dim3(blocks), dim3(256), 0, st, n, hw, c, (const bf16*)x, feat);
+  else if (dtype == ARGUS_F16)
+    hipLaunchKernelGGL(avgpool_fwd_kernel<f16>, dim3(blocks), dim3(256), 0, st, n, hw, c, (const f16*)x, feat);
   else
     hipLaunchKernelGGL(avgpool_fwd_kernel<float>, dim3(blocks), dim3(256), 0, st, n, hw, c, (const float*)x, feat);
   return check_launch("avgpool_fwd_kernel");
 }
 
 int argus_avgpool_bwd(int dtype, int n, int hw, int c, const float* dfeat, void* dx, argus_stream_t stream) {
+  if (f16_unserved(dtype, "avgpool_bwd")) return ARGUS_ERR_ARG;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
   if (c % E) { set_error("avgpool_bwd: bad channels"); return ARGUS_ERR_SHAPE; }
   const int64_t nch = (int64_t)n * hw * c / E;

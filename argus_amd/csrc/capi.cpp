@@ -12,6 +12,12 @@ static thread_local std::string g_last_error;
 
 void set_error(const std::string& msg) { g_last_error = msg; }
 
+bool f16_unserved(int dtype, const char* who) {
+  if (dtype != ARGUS_F16) return false;
+  set_error(std::string(who) + ": dtype ARGUS_F16 is served by the frozen-inference entry points only");
+  return true;
+}
+
 int check_launch(const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -44,6 +50,7 @@ int argus_images_u8_to_nhwc4(int dtype, int64_t nimg, int h, int w, const uint8_
 
 int argus_conv_weight_prep(const argus_conv_desc* d, int dtype, const float* w, const int64_t* strides, void* wf,
                            void* wd, argus_stream_t stream) {
+  if (d && !d->stem && f16_unserved(dtype, "conv_weight_prep (not a stem descriptor)")) return ARGUS_ERR_ARG;
   if (!d || !w) { set_error("conv_weight_prep: null argument"); return ARGUS_ERR_ARG; }
   return conv_weight_prep(*d, dtype, w, strides, wf, wd, (hipStream_t)stream);
 }
@@ -57,11 +64,13 @@ int argus_conv_weight_prep_table(int count, const argus_conv_desc* descs, const 
 }
 
 int argus_conv_weight_prep_batch(int dtype, int count, const void* device_table, int nblocks, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_weight_prep_batch")) return ARGUS_ERR_ARG;
   return conv_weight_prep_batch(dtype, count, device_table, nblocks, (hipStream_t)stream);
 }
 
 int argus_conv_fwd(const argus_conv_desc* d, int dtype, const void* x, const void* w, void* y, const float* sc,
                    const float* sh, float* stats, argus_stream_t stream) {
+  if (d && (!d->stem || sc || sh || stats) && f16_unserved(dtype, "conv_fwd (not a plain stem forward)")) return ARGUS_ERR_ARG;
   if (!d || !x || !w || (!y && !stats) || (sc == nullptr) != (sh == nullptr)) {
     set_error("conv_fwd: bad arguments");
     return ARGUS_ERR_ARG;
@@ -71,6 +80,7 @@ int argus_conv_fwd(const argus_conv_desc* d, int dtype, const void* x, const voi
 
 int argus_conv_fwd_fin(const argus_conv_desc* d, int dtype, const void* x, const void* w, void* y, const float* sc,
                        const float* sh, float* stats, const argus_bn_fwd_fin* fin, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_fwd_fin")) return ARGUS_ERR_ARG;
   if (!d || !x || !w || !stats || !fin || !fin->workspace || !fin->gamma || !fin->beta ||
       (sc == nullptr) != (sh == nullptr)) {
     set_error("conv_fwd_fin: bad arguments");
@@ -89,6 +99,7 @@ int argus_conv_fwd_fin(const argus_conv_desc* d, int dtype, const void* x, const
 
 int argus_conv_fwd_apply_out(const argus_conv_desc* d, int dtype, const void* x, const void* w, void* y,
                              const float* sc, const float* sh, float* stats, void* x_out, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_fwd_apply_out")) return ARGUS_ERR_ARG;
   if (!d || !x || !w || (!y && !stats) || !sc || !sh || !x_out) {
     set_error("conv_fwd_apply_out: bad arguments");
     return ARGUS_ERR_ARG;
@@ -99,6 +110,7 @@ int argus_conv_fwd_apply_out(const argus_conv_desc* d, int dtype, const void* x,
 int argus_conv_fwd_bn_out(const argus_conv_desc* d, int dtype, const void* x, const void* w_fwd, const float* scale,
                           const float* shift, const void* res, const float* res_scale, const float* res_shift, void* out,
                           uint8_t* mask_bits, void* y, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_fwd_bn_out")) return ARGUS_ERR_ARG;
   if (!d) {
     set_error("conv_fwd_bn_out: bad arguments");
     return ARGUS_ERR_ARG;
@@ -106,14 +118,20 @@ int argus_conv_fwd_bn_out(const argus_conv_desc* d, int dtype, const void* x, co
   return conv_fwd_bn_out(*d, dtype, x, w_fwd, scale, shift, res, res_scale, res_shift, out, mask_bits, y,
                          (hipStream_t)stream);
 }
-int argus_conv_fwd_stat_rows(const argus_conv_desc* d, int dtype) { return d ? conv_fwd_stat_rows(*d, dtype) : 0; }
+int argus_conv_fwd_stat_rows(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_fwd_stat_rows")) return 0;
+  return d ? conv_fwd_stat_rows(*d, dtype) : 0;
+}
 int argus_conv_fwd_stats_only_rows(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_fwd_stats_only_rows")) return 0;
   return d ? conv_fwd_stats_only_rows(*d, dtype) : 0;
 }
 int argus_conv_fwd_stats_only_tile(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_fwd_stats_only_tile")) return 0;
   return d ? conv_fwd_stats_only_tile(*d, dtype) : 0;
 }
 size_t argus_conv_fwd_stat_part_bytes(const argus_conv_desc* d, int dtype, int stats_only) {
+  if (f16_unserved(dtype, "conv_fwd_stat_part_bytes")) return 0;
   if (!d || conv_check_desc(*d)) return 0;
   const int rows = stats_only ? conv_fwd_stats_only_rows(*d, dtype) : conv_fwd_stat_rows(*d, dtype);
   const int tile = stats_only ? conv_fwd_stats_only_tile(*d, dtype) : conv_fwd_stat_tile(*d, dtype);
@@ -152,26 +170,36 @@ int argus_conv_infer(const argus_conv_desc* d, int dtype, const void* x, const v
 int argus_conv_policy_default(int key) { return policy_default(key); }
 
 int argus_conv_launch_info(const argus_conv_desc* d, int dtype, int pass, int64_t* flops) {
+  if (f16_unserved(dtype, "conv_launch_info")) return -1;
   return d ? conv_launch_info(*d, dtype, pass, flops) : -1;
 }
 
-int argus_conv_fwd_stat_tile(const argus_conv_desc* d, int dtype) { return d ? conv_fwd_stat_tile(*d, dtype) : 0; }
+int argus_conv_fwd_stat_tile(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_fwd_stat_tile")) return 0;
+  return d ? conv_fwd_stat_tile(*d, dtype) : 0;
+}
 
 int argus_conv_dgrad(const argus_conv_desc* d, int dtype, const void* dy, const void* wt, void* dx, const void* addend,
                      const uint8_t* addend_mask,
                      argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_dgrad")) return ARGUS_ERR_ARG;
   if (!d || !dy || !wt || !dx) { set_error("conv_dgrad: bad arguments"); return ARGUS_ERR_ARG; }
   return conv_dgrad(*d, dtype, dy, wt, dx, addend, addend_mask, (hipStream_t)stream);
 }
 
-int argus_conv_dgrad_bn_rows(const argus_conv_desc* d, int dtype) { return d ? conv_dgrad_bn_rows(*d, dtype) : -1; }
+int argus_conv_dgrad_bn_rows(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_dgrad_bn_rows")) return -1;
+  return d ? conv_dgrad_bn_rows(*d, dtype) : -1;
+}
 int argus_conv_dgrad_stages_prologue(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_dgrad_stages_prologue")) return 0;
   return d ? conv_dgrad_stages_prologue(*d, dtype) : 0;
 }
 
 int argus_conv_dgrad_bn(const argus_conv_desc* d, int dtype, const void* dy, const void* wt, void* dm,
                         const void* addend, const argus_bn_bwd_epilogue* bn, const argus_bn_bwd_prologue* pro,
                         argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_dgrad_bn")) return ARGUS_ERR_ARG;
   if (!d || !dy || !wt || !dm) { set_error("conv_dgrad_bn: bad arguments"); return ARGUS_ERR_ARG; }
   return conv_dgrad_bn(*d, dtype, dy, wt, dm, addend, bn, pro, (hipStream_t)stream);
 }
@@ -192,25 +220,30 @@ int argus_conv_dgrad_bn_x8(const argus_conv_desc* d, const void* dy8, const void
 
 int argus_conv_wgrad_apply(const argus_conv_desc* d, int dtype, const void* x, const void* dm,
                            const argus_bn_bwd_prologue* ap, float* dw, void* ws, size_t ws_bytes, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_wgrad_apply")) return ARGUS_ERR_ARG;
   if (!d || !x || !dm || !ap || !dw || !ws) { set_error("conv_wgrad_apply: bad arguments"); return ARGUS_ERR_ARG; }
   return conv_wgrad_apply(*d, dtype, x, dm, *ap, dw, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int argus_conv_stem_dgrad(const argus_conv_desc* d, int dtype, const void* dy, const void* w_fwd,
                           const argus_bn_bwd_prologue* ap, float* dx_nchw, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_stem_dgrad")) return ARGUS_ERR_ARG;
   if (!d || !dy || !w_fwd || !dx_nchw) { set_error("conv_stem_dgrad: null argument"); return ARGUS_ERR_ARG; }
   return conv_stem_dgrad(*d, dtype, dy, w_fwd, ap, dx_nchw, (hipStream_t)stream);
 }
 
 int argus_conv_dgrad_wgrad_ok(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_dgrad_wgrad_ok")) return 0;
   return d && !conv_check_desc(*d) && conv_dgw_ok(*d, dtype) ? 1 : 0;
 }
 
 size_t argus_conv_dgrad_wgrad_workspace_bytes(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_dgrad_wgrad_workspace_bytes")) return 0;
   return d && !conv_check_desc(*d) ? conv_dgw_ws_bytes(*d, dtype) : 0;
 }
 
 int argus_conv_dgrad_wgrad_bn_rows(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_dgrad_wgrad_bn_rows")) return -1;
   return d && !conv_check_desc(*d) ? conv_dgw_rows(*d, dtype) : -1;
 }
 
@@ -218,15 +251,20 @@ int argus_conv_dgrad_wgrad_bn(const argus_conv_desc* d, int dtype, const void* d
                               const void* x, void* dx, const void* addend, const argus_bn_bwd_epilogue* bn,
                               const argus_bn_bwd_prologue* pro, float* dw, void* workspace,
                               size_t workspace_bytes, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_dgrad_wgrad_bn")) return ARGUS_ERR_ARG;
   if (!d) { set_error("conv_dgrad_wgrad_bn: bad arguments"); return ARGUS_ERR_ARG; }
   return conv_dgw(*d, dtype, dm, w_dgrad, x, dx, addend, bn, pro, dw, workspace, workspace_bytes,
                   (hipStream_t)stream);
 }
 
-size_t argus_conv_wgrad_workspace_bytes(const argus_conv_desc* d, int dtype) { return d ? conv_wgrad_ws(*d, dtype) : 0; }
+size_t argus_conv_wgrad_workspace_bytes(const argus_conv_desc* d, int dtype) {
+  if (f16_unserved(dtype, "conv_wgrad_workspace_bytes")) return 0;
+  return d ? conv_wgrad_ws(*d, dtype) : 0;
+}
 
 int argus_conv_wgrad(const argus_conv_desc* d, int dtype, const void* x, const float* sc, const float* sh,
                      const void* dy, float* dw, void* ws, size_t ws_bytes, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_wgrad")) return ARGUS_ERR_ARG;
   if (!d || !x || !dy || !dw || !ws || (sc == nullptr) != (sh == nullptr)) {
     set_error("conv_wgrad: bad arguments");
     return ARGUS_ERR_ARG;

@@ -1,7 +1,8 @@
 // Shared device helpers for the argus MI355X (gfx950 / CDNA4) kernels.
 //
 // Storage types: activations/weights are either fp32 (`float`, the parity path) or bf16
-// (`__bf16`, the throughput path). Every reduction, BN statistic, loss and optimizer value is fp32
+// (`__bf16`, the throughput path); a frozen inference session may also store them as IEEE fp16 (`_Float16`,
+// ARGUS_F16: forward kernels only). Every reduction, BN statistic, loss and optimizer value is fp32
 // (doubles where a reduction crosses many workgroups).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,8 +12,11 @@
 #define ARGUS_HOST_DEV __host__ __device__
 
 typedef __bf16 bf16;
+typedef _Float16 f16;  // IEEE binary16: the frozen-inference storage type (ARGUS_F16), never a training dtype
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
@@ -58,14 +62,24 @@ ARGUS_DEV int fdiv(int n, const FastDiv& f) {
 
 ARGUS_DEV float to_f32(float x) { return x; }
 ARGUS_DEV float to_f32(bf16 x) { return (float)x; }
+ARGUS_DEV float to_f32(f16 x) { return (float)x; }
 template <typename T> ARGUS_DEV T from_f32(float x);
 template <> ARGUS_DEV float from_f32<float>(float x) { return x; }
 template <> ARGUS_DEV bf16 from_f32<bf16>(float x) { return (bf16)x; }
+// fp16 saturates: round to nearest even after a clamp to the largest finite value (+-65504), so an
+// overflowing activation stays finite and the next conv never sees inf - inf. NaN stays NaN (v_med3_f32
+// returns a bound for a NaN input, hence the select).
+constexpr float kF16Max = 65504.f;
+template <> ARGUS_DEV f16 from_f32<f16>(float x) {
+  const float c = __builtin_amdgcn_fmed3f(x, -kF16Max, kF16Max);
+  return (f16)(x != x ? x : c);
+}
 
-// A 16-byte "chunk": 8 bf16 or 4 fp32 elements. All activation and weight traffic moves in chunks.
+// A 16-byte "chunk": 8 bf16 / fp16 or 4 fp32 elements. All activation and weight traffic moves in chunks.
 template <typename T> struct Chunk;
 template <> struct Chunk<float> { static constexpr int E = 4; };
 template <> struct Chunk<bf16> { static constexpr int E = 8; };
+template <> struct Chunk<f16> { static constexpr int E = 8; };
 
 ARGUS_DEV u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p); }
 ARGUS_DEV void st16(void* p, u32x4 v) { *reinterpret_cast<u32x4*>(p) = v; }
@@ -100,6 +114,26 @@ ARGUS_DEV u32x4 pack(const float (&f)[8]) {
   u32x4 v; v.x = pack2_bf16(f[0], f[1]); v.y = pack2_bf16(f[2], f[3]);
   v.z = pack2_bf16(f[4], f[5]); v.w = pack2_bf16(f[6], f[7]); return v;
 }
+
+// The typed forms: the element type picks the 16-bit format (the overloads above cannot tell fp16 from
+// bf16 by the lane count). For float / bf16 they are the overloads above.
+template <typename T> struct ChunkCvt {
+  static ARGUS_DEV void unpack(u32x4 v, float (&f)[Chunk<T>::E]) { argus::unpack(v, f); }
+  static ARGUS_DEV u32x4 pack(const float (&f)[Chunk<T>::E]) { return argus::pack(f); }
+};
+template <> struct ChunkCvt<f16> {
+  static ARGUS_DEV void unpack(u32x4 v, float (&f)[8]) {
+    const f16x8 h = __builtin_bit_cast(f16x8, v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = (float)h[i];
+  }
+  static ARGUS_DEV u32x4 pack(const float (&f)[8]) {
+    f16x8 h;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = from_f32<f16>(f[i]);
+    return __builtin_bit_cast(u32x4, h);
+  }
+};
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 ARGUS_DEV v8i cat8(u32x4 lo, u32x4 hi) {

@@ -1723,10 +1723,15 @@ int conv_fwd(const argus_conv_desc& d, int dtype, const void* x, const void* w, 
     set_error("conv_fwd_apply_out: a BN+ReLU prologue on a 1x1 stride-1 bf16/fp32 conv, x_out != x");
     return ARGUS_ERR_ARG;
   }
+  // fp16 (frozen inference): the plain stem forward alone; argus_conv_fwd rejects the rest first
+  if (dtype == ARGUS_F16 && (!d.stem || sc || stats || pro_out || fin || !y)) {
+    set_error("conv_fwd: dtype ARGUS_F16 serves the plain stem forward only");
+    return ARGUS_ERR_ARG;
+  }
   const bool f8 = dtype == ARGUS_FP8;  // bf16 tensors, MX-fp8 GEMM operands where the shape allows
   if (f8) dtype = ARGUS_BF16;
   g_launch_work = 2.0 * d.n * d.ho * d.wo * d.k * d.r * d.s * d.c;  // algorithmic flops / bytes (ktimer)
-  g_launch_bytes = (double)(dtype == ARGUS_BF16 ? 2 : 4) *
+  g_launch_bytes = (double)(dtype == ARGUS_F32 ? 4 : 2) *
                        ((double)d.n * d.h * d.w * (d.stem ? 4 : d.c) + (double)d.k * d.r * d.s * d.c +
                         (double)d.n * d.ho * d.wo * d.k) +
                    (stats ? 8.0 * conv_fwd_stat_rows(d, dtype) * d.k : 0.0);
@@ -1758,7 +1763,7 @@ int conv_fwd(const argus_conv_desc& d, int dtype, const void* x, const void* w, 
     ff.mean_o = fin->mean; ff.invstd_o = fin->invstd; ff.scale_o = fin->scale; ff.shift_o = fin->shift;
   }
   const BnFwdFin* ffp = ff.mode ? &ff : nullptr;
-  if (stem_lds_fwd(d, dtype, pol) && stem_fwd_launch(d, dtype, x, w, y, stats, st, ffp))  // stem.hip (bf16)
+  if (stem_lds_fwd(d, dtype, pol) && stem_fwd_launch(d, dtype, x, w, y, stats, st, ffp))  // stem.hip (bf16, fp16)
     return check_launch("stem_fwd_kernel");
   if (!y && !sc && p1x1_fwd_stats_ok(d, dtype, pol[kP1x1FwdStats]))  // statistics only: conv_p1x1.hip
     return p1x1_fwd_stats_launch(d, x, w, stats, st, ffp);
@@ -1770,6 +1775,10 @@ int conv_fwd(const argus_conv_desc& d, int dtype, const void* x, const void* w, 
   const int bm = fwd_bm(d, pol), bn = d.stem ? 64 : pick_bn(pol, 0, d.k);
   p.stat_tile = bm;
   p.f8 = f8;
+  if (dtype == ARGUS_F16) {  // a stem frame too ragged for the LDS-patch kernel: the STEM igemm bf16 takes
+    launch_ig<f16, 128, 64, true, false, 4>(p, p.ph[0].M, st);
+    return check_launch("igemm_kernel");
+  }
   return dtype == ARGUS_BF16 ? run_ig<bf16>(p, st, bm, bn) : run_ig<float>(p, st, bm, bn);
 }
 
@@ -2223,6 +2232,9 @@ int conv_weight_prep(const argus_conv_desc& d, int dtype, const float* w, const 
   if (dtype == ARGUS_BF16)
     hipLaunchKernelGGL(weight_prep_kernel<bf16>, dim3(blocks), dim3(256), 0, st, w, ws, (bf16*)wf,
                        (bf16*)(d.stem ? nullptr : wd), d.k, d.r, d.s, d.c, d.stem);
+  else if (dtype == ARGUS_F16)  // the stem of a frozen fp16 session: w_fwd alone (argus_conv_weight_prep checked)
+    hipLaunchKernelGGL(weight_prep_kernel<f16>, dim3(blocks), dim3(256), 0, st, w, ws, (f16*)wf, (f16*)nullptr, d.k,
+                       d.r, d.s, d.c, d.stem);
   else
     hipLaunchKernelGGL(weight_prep_kernel<float>, dim3(blocks), dim3(256), 0, st, w, ws, (float*)wf,
                        (float*)(d.stem ? nullptr : wd), d.k, d.r, d.s, d.c, d.stem);
@@ -2277,6 +2289,8 @@ static int launch_images(int dtype, int64_t nimg, int h, int w, const In* x, voi
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
   if (dtype == ARGUS_BF16)
     hipLaunchKernelGGL((images_to_nhwc4_kernel<bf16, In>), dim3(blocks), dim3(256), 0, st, x, (bf16*)out, nimg, h * w);
+  else if (dtype == ARGUS_F16)
+    hipLaunchKernelGGL((images_to_nhwc4_kernel<f16, In>), dim3(blocks), dim3(256), 0, st, x, (f16*)out, nimg, h * w);
   else
     hipLaunchKernelGGL((images_to_nhwc4_kernel<float, In>), dim3(blocks), dim3(256), 0, st, x, (float*)out, nimg,
                        h * w);

@@ -38,7 +38,8 @@ struct InferParams {
 };
 
 // ---- fold ---------------------------------------------------------------------------------------------
-// w_fold[k][r][s][c] = T(w[k][c][r][s] * scale[k]) (one fp32 multiply, then round to nearest even),
+// w_fold[k][r][s][c] = T(w[k][c][r][s] * scale[k]) (one fp32 multiply, then round to nearest even; fp16
+// saturates to +-65504: from_f32<f16>),
 // bias[k] = shift[k]; scale / shift = bn_eval_coeff (bnfin.h)
 struct FoldStrides { long long sk, sc, sr, ss; };
 
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(256, 2) void conv_infer_kernel(const InferParams p)
     }
     if (Rs) {
       float r[E];
-      unpack(rv[it], r);
+      ChunkCvt<T>::unpack(rv[it], r);
 #pragma unroll
       for (int j = 0; j < E; ++j) f[j] += r[j];
     }
@@ -308,17 +309,18 @@ __global__ __launch_bounds__(256, 2) void conv_infer_kernel(const InferParams p)
 #pragma unroll
       for (int j = 0; j < E; ++j) f[j] = fmaxf(f[j], 0.f);
     }
-    st16(O + (size_t)m * p.K + col, pack(f));
+    st16(O + (size_t)m * p.K + col, ChunkCvt<T>::pack(f));
   }
 }
 
 // ---- host ---------------------------------------------------------------------------------------------
-static bool infer_dtype_ok(int dtype) { return dtype == ARGUS_F32 || dtype == ARGUS_BF16; }
+static bool infer_dtype_ok(int dtype) { return dtype == ARGUS_F32 || dtype == ARGUS_BF16 || dtype == ARGUS_F16; }
+static bool infer_16bit(int dtype) { return dtype == ARGUS_BF16 || dtype == ARGUS_F16; }
 
 // the four non-stem conv kinds of ResNet-50; sets the error message when not served
 static int infer_check(const argus_conv_desc& d, int dtype, const char* who) {
   if (!infer_dtype_ok(dtype)) {
-    set_error(std::string(who) + ": dtype must be ARGUS_F32 or ARGUS_BF16");
+    set_error(std::string(who) + ": dtype must be ARGUS_F32, ARGUS_BF16 or ARGUS_F16");
     return ARGUS_ERR_ARG;
   }
   if (int e = conv_check_desc(d)) return e;
@@ -331,7 +333,7 @@ static int infer_check(const argus_conv_desc& d, int dtype, const char* who) {
   return ARGUS_OK;
 }
 
-static int infer_bke(int dtype) { return dtype == ARGUS_BF16 ? 64 : 32; }
+static int infer_bke(int dtype) { return infer_16bit(dtype) ? 64 : 32; }
 static int infer_nk(const argus_conv_desc& d, int dtype) { return d.r * d.s * d.c / infer_bke(dtype); }
 // 32-row tiles while 64-row tiles would not give every CU one
 static int infer_bm(const argus_conv_desc& d) {
@@ -354,7 +356,7 @@ int conv_infer_max_splits(const argus_conv_desc& d, int dtype) {
 int conv_infer_splits(const argus_conv_desc& d, int dtype) {
   if (infer_check(d, dtype, "conv_infer_splits")) return 0;
   const int tiles = infer_tiles(d), nk = infer_nk(d, dtype);
-  const int step = dtype == ARGUS_BF16 ? 300 : 500;  // ns per k-step
+  const int step = infer_16bit(dtype) ? 300 : 500;  // ns per k-step (fp16: bf16's fit, reused unfitted)
   int best = 1, best_cost = step * nk;
   for (int s = 2; s <= kInferMaxSplits && s <= nk && tiles * s <= kInferCUs; s *= 2) {
     const int cost = step * cdiv(nk, s) + 600 + 14 * tiles * s;
@@ -380,6 +382,9 @@ int conv_fold_bn(const argus_conv_desc& d, int dtype, const float* w, const int6
   if (dtype == ARGUS_BF16)
     hipLaunchKernelGGL(fold_bn_kernel<bf16>, dim3(blocks), dim3(256), 0, st, w, fs, gamma, beta, rm, rv, eps,
                        (bf16*)wf, bias, d.k, d.r, d.s, d.c);
+  else if (dtype == ARGUS_F16)
+    hipLaunchKernelGGL(fold_bn_kernel<f16>, dim3(blocks), dim3(256), 0, st, w, fs, gamma, beta, rm, rv, eps,
+                       (f16*)wf, bias, d.k, d.r, d.s, d.c);
   else
     hipLaunchKernelGGL(fold_bn_kernel<float>, dim3(blocks), dim3(256), 0, st, w, fs, gamma, beta, rm, rv, eps,
                        (float*)wf, bias, d.k, d.r, d.s, d.c);
@@ -429,11 +434,12 @@ int conv_infer(const argus_conv_desc& d, int dtype, const void* x, const void* w
   p.nk = nk; p.splits = splits; p.relu = relu; p.ntiles = d.k / kInferBN;
   p.fd_hw = make_fastdiv(d.ho * d.wo); p.fd_w = make_fastdiv(d.wo);
   p.fd_c = make_fastdiv(d.c); p.fd_s = make_fastdiv(d.s);
-  const double es = dtype == ARGUS_BF16 ? 2.0 : 4.0, px = (double)p.M;
+  const double es = infer_16bit(dtype) ? 2.0 : 4.0, px = (double)p.M;
   g_launch_work = 2.0 * px * d.k * p.RSC;
   g_launch_bytes = es * ((double)d.n * d.h * d.w * d.c + (double)d.k * p.RSC + px * d.k * (res ? 2 : 1)) + 4.0 * d.k;
   const dim3 grid(cdiv(p.M, bm) * p.ntiles, 1, splits);
   if (dtype == ARGUS_BF16) infer_launch<bf16>(p, bm, grid, st);
+  else if (dtype == ARGUS_F16) infer_launch<f16>(p, bm, grid, st);
   else infer_launch<float>(p, bm, grid, st);
   return check_launch("conv_infer_kernel");
 }

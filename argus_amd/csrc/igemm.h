@@ -123,6 +123,12 @@ template <> struct Mma<bf16> {
                                                   __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
   }
 };
+template <> struct Mma<f16> {  // v_mfma_f32_16x16x32_f16: bf16's shape and rate
+  static ARGUS_DEV void run(f32x4& acc, u32x4 a, u32x4 b) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0,
+                                                 0);
+  }
+};
 template <> struct Mma<float> {
   // lane group g supplies k = 4g + j at sub-step j (same mapping for A and B)
   static ARGUS_DEV void run(f32x4& acc, u32x4 a, u32x4 b) {
@@ -285,11 +291,11 @@ ARGUS_DEV u32x4 epi_apply(const IgParams& p, u32x4 v, const EpiIn& in, BwdEpiAcc
   constexpr int E = Chunk<T>::E;
   if (p.addend) {
     float f[E], o[E];
-    unpack(v, f);
-    unpack(in.add, o);
+    ChunkCvt<T>::unpack(v, f);
+    ChunkCvt<T>::unpack(in.add, o);
 #pragma unroll
     for (int j = 0; j < E; ++j) f[j] += (in.amask >> j) & 1u ? o[j] : 0.f;
-    v = pack(f);
+    v = ChunkCvt<T>::pack(f);
   }
   if constexpr (BW != 0) v = bwd.step(v, in.y, in.y2, in.bits);
   return v;

@@ -11,6 +11,10 @@ namespace argus {
 
 void set_error(const std::string& msg);
 int check_launch(const char* what);
+// ARGUS_F16 is served by the frozen-inference entry points alone (argus_hip.h lists them). Every other
+// extern "C" entry that takes a dtype calls this first: true (and the "dtype" error set) for ARGUS_F16, so
+// no launcher that picks `dtype == ARGUS_BF16 ? bf16 : float` ever sees 2-byte tensors as fp32.
+bool f16_unserved(int dtype, const char* who);
 
 int conv_fwd_bn_out(const argus_conv_desc& d, int dtype, const void* x, const void* w, const float* sc,
                     const float* sh, const void* res, const float* rsc, const float* rsh, void* out, uint8_t* bits,

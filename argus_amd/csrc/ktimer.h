@@ -33,6 +33,8 @@ inline void timed_launch(const char* name, K kernel, dim3 grid, dim3 block, hipS
 
 template <typename T>
 inline const char* type_name() { return sizeof(T) == 2 ? "__bf16" : "float"; }
+template <>
+inline const char* type_name<_Float16>() { return "_Float16"; }
 inline const char* bool_name(bool b) { return b ? "true" : "false"; }
 
 }  // namespace argus

@@ -1,5 +1,6 @@
 // ResNet-50 stem convolution (torchvision conv1: 7x7, stride 2, pad 3, 3 -> 64 channels, bias=False;
-// argus/models.py:43) forward, bf16, with the input patch of each output tile staged in LDS once.
+// argus/models.py:43) forward, bf16 (and fp16 for a frozen session: the 16-bit type is a template parameter
+// of the forward kernel only), with the input patch of each output tile staged in LDS once.
 //
 // Why: the implicit GEMM (conv.hip, STEM variant) gathers its im2col operand from global memory per
 // k-step: every input pixel is fetched by ~12 output pixels (49 taps at stride 2), and its K of 256
@@ -28,9 +29,7 @@
 // a workgroup stages dy (staged through the BN-backward apply when fused) and the patch once per
 // 256-pixel tile, loops over its run of tiles with the next tile's loads in flight, and writes one
 // fp32 64 x 256 partial per split for wgrad_reduce_kernel.
-#include "common.h"
-#include "bnfin.h"
-#include "internal.h"
+#include "igemm.h"
 #include "ktimer.h"
 
 namespace argus {
@@ -46,10 +45,11 @@ constexpr int kLD = 64 + 8;                // C staging row stride, elements
 constexpr int kLdsB = (kPatchB + kWB) > 256 * kLD * 2 ? (kPatchB + kWB) : 256 * kLD * 2;
 }  // namespace
 
+template <typename T>
 struct StemParams {
-  const bf16* x;   // (n, H, W, 4) bf16, channel 3 zero
-  const bf16* w;   // w_fwd of the stem: [64][8][8][4] (r, s, c), padding zero
-  bf16* y;         // (n, Ho, Wo, 64)
+  const T* x;      // (n, H, W, 4) bf16 / fp16, channel 3 zero
+  const T* w;      // w_fwd of the stem: [64][8][8][4] (r, s, c), padding zero
+  T* y;            // (n, Ho, Wo, 64)
   float2* stats;   // {sum, M2} per 128 output pixels x 64 channels, or null
   int* counts;     // ragged tilings: pixels per partial row (after the partials), else null
   int n, H, W, Ho, Wo;
@@ -59,10 +59,12 @@ struct StemParams {
 ARGUS_HOST_DEV inline int stem_tpr(int wo) { return (wo + kTW - 1) / kTW; }
 ARGUS_HOST_DEV inline int stem_tpi(int ho, int wo) { return ((ho + kTH - 1) / kTH) * stem_tpr(wo); }
 
-__global__ __launch_bounds__(256, 3) void stem_fwd_kernel(const StemParams p) {
+template <typename T>
+__global__ __launch_bounds__(256, 3) void stem_fwd_kernel(const StemParams<T> p) {
+  static_assert(sizeof(T) == 2, "stem_fwd_kernel: bf16 or fp16");
   __shared__ __attribute__((aligned(16))) uint8_t lds[kLdsB];
   uint2* patch = reinterpret_cast<uint2*>(lds);
-  bf16* wl = reinterpret_cast<bf16*>(lds + kPatchB);
+  T* wl = reinterpret_cast<T*>(lds + kPatchB);
 
   const int tpr = stem_tpr(p.Wo), tpi = stem_tpi(p.Ho, p.Wo);  // tiles per tile-row, per image
   const int tile = xcd_remap(blockIdx.x, gridDim.x);
@@ -126,8 +128,7 @@ __global__ __launch_bounds__(256, 3) void stem_fwd_kernel(const StemParams p) {
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[mi]),
-                                                              __builtin_bit_cast(bf16x8, fb[ni]), acc[mi][ni], 0, 0, 0);
+        Mma<T>::run(acc[mi][ni], fa[mi], fb[ni]);
   }
   __syncthreads();  // LDS is reused below
 
@@ -199,14 +200,14 @@ __global__ __launch_bounds__(256, 3) void stem_fwd_kernel(const StemParams p) {
   }
 
   // ---- epilogue: C tile through LDS, 16-byte coalesced non-temporal stores ----
-  bf16* Cs = reinterpret_cast<bf16*>(lds);
+  T* Cs = reinterpret_cast<T*>(lds);
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        Cs[(wave * 64 + mi * 16 + g * 4 + r) * kLD + ni * 16 + i16] = (bf16)acc[mi][ni][r];
+        Cs[(wave * 64 + mi * 16 + g * 4 + r) * kLD + ni * 16 + i16] = from_f32<T>(acc[mi][ni][r]);
   __syncthreads();
   const int c = tid & 7;
 #pragma unroll
@@ -374,9 +375,10 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_kernel(const StemWgParams p
         out[(16 * (2 * wm + m2) + 4 * g + e) * 256 + 16 * (7 * wn + t7) + i16] = acc[m2][t7][e];
 }
 
-// bf16, 64 output channels, and an 8 x 32 tiling of the output that is >= 75 % pixels of the image
-static bool stem_shape_ok(const argus_conv_desc& d, int dtype) {
-  if (dtype != ARGUS_BF16 || !d.stem || d.k != 64) return false;
+// bf16 (the forward also fp16), 64 output channels, and an 8 x 32 tiling of the output that is >= 75 %
+// pixels of the image
+static bool stem_shape_ok(const argus_conv_desc& d, int dtype, bool fwd = false) {
+  if (!(dtype == ARGUS_BF16 || (fwd && dtype == ARGUS_F16)) || !d.stem || d.k != 64) return false;
   const long tiled = (long)stem_tpi(d.ho, d.wo) * kTH * kTW;
   return 4L * d.ho * d.wo >= 3L * tiled;
 }
@@ -413,19 +415,19 @@ bool stem_wgrad_launch(const argus_conv_desc& d, int dtype, const void* x, const
   return true;
 }
 
-bool stem_fwd_ok(const argus_conv_desc& d, int dtype) { return stem_shape_ok(d, dtype); }
+bool stem_fwd_ok(const argus_conv_desc& d, int dtype) { return stem_shape_ok(d, dtype, true); }
 
 // The partial-row layout this kernel writes is argus_conv_fwd_stat_rows / _stat_tile: stem_stat_rows
 // rows of 128 pixels (-128 when ragged: int32 pixel counts per row follow the float2[rows][64] partials)
-bool stem_fwd_launch(const argus_conv_desc& d, int dtype, const void* x, const void* w, void* y, float* stats,
-                     hipStream_t st, const BnFwdFin* ffin) {
-  if (!stem_fwd_ok(d, dtype)) return false;
-  StemParams p;
+template <typename T>
+static void stem_fwd_run(const argus_conv_desc& d, const void* x, const void* w, void* y, float* stats, hipStream_t st,
+                         const BnFwdFin* ffin, const char* name) {
+  StemParams<T> p;
   p.ffin = BnFwdFin{};
   if (ffin && stats) {  // the folded finalize: two partial rows a tile (argus_conv_fwd_fin)
     p.ffin = *ffin;
-    const int T = d.n * stem_tpi(d.ho, d.wo);
-    if (bn_fwd_fin_plan(p.ffin, T, 2, stem_stat_rows(d))) {
+    const int tiles = d.n * stem_tpi(d.ho, d.wo);
+    if (bn_fwd_fin_plan(p.ffin, tiles, 2, stem_stat_rows(d))) {
       p.ffin.tile_rows = stem_ragged(d) ? -128 : 128;
       p.ffin.part = reinterpret_cast<const float2*>(stats);
       g_ffin_folded = 1;
@@ -433,14 +435,25 @@ bool stem_fwd_launch(const argus_conv_desc& d, int dtype, const void* x, const v
       p.ffin.mode = 0;
     }
   }
-  p.x = reinterpret_cast<const bf16*>(x);
-  p.w = reinterpret_cast<const bf16*>(w);
-  p.y = reinterpret_cast<bf16*>(y);
+  p.x = reinterpret_cast<const T*>(x);
+  p.w = reinterpret_cast<const T*>(w);
+  p.y = reinterpret_cast<T*>(y);
   p.stats = reinterpret_cast<float2*>(stats);
   p.counts = stats && stem_ragged(d) ? reinterpret_cast<int*>(p.stats + (size_t)stem_stat_rows(d) * 64) : nullptr;
   p.n = d.n; p.H = d.h; p.W = d.w; p.Ho = d.ho; p.Wo = d.wo;
   const int grid = d.n * stem_tpi(d.ho, d.wo);
-  timed_launch("argus::stem_fwd_kernel", stem_fwd_kernel, dim3(grid), dim3(256), st, p);
+  timed_launch(name, stem_fwd_kernel<T>, dim3(grid), dim3(256), st, p);
+}
+
+bool stem_fwd_launch(const argus_conv_desc& d, int dtype, const void* x, const void* w, void* y, float* stats,
+                     hipStream_t st, const BnFwdFin* ffin) {
+  if (!stem_fwd_ok(d, dtype)) return false;
+  if (dtype == ARGUS_F16) {  // frozen inference: no statistics in fp16 (argus_conv_fwd rejects them)
+    if (stats) return false;
+    stem_fwd_run<f16>(d, x, w, y, nullptr, st, nullptr, "argus::stem_fwd_kernel<_Float16>");
+  } else {
+    stem_fwd_run<bf16>(d, x, w, y, stats, st, ffin, "argus::stem_fwd_kernel");  // the timer name it always had
+  }
   return true;
 }
 

@@ -12,6 +12,11 @@ and picks tiles for tens of thousands of GEMM rows. A session freezes the model 
 - activations rotate through five buffers, nothing is saved per layer;
 - everything is issued on one stream in program order, so the captured graph is a linear chain.
 
+``compute_dtype="fp16"`` (chosen explicitly; there is no fp16 training) runs the same launches on IEEE half
+tensors: bf16's MFMA rate and bytes with 8x smaller rounding steps, at the price of range. Every fp16 store
+saturates to +-65504, ``refresh()`` refuses a checkpoint whose folded weights do not fit, and
+``activation_peak`` reports the headroom of the activations on given frames.
+
 The session is a snapshot: later changes to the model show only after ``refresh()``, and the session never
 writes to the model. It replaces ``self.resnet(x)`` + the head of ``NCameraCNN.forward`` in eval mode
 (argus/models.py:66-90) behind ``get_pose`` (argus/utils.py:179-189).
@@ -23,12 +28,14 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from argus_amd._lib import BF16, F32, ConvDesc, lib, ptr, stream
+from argus_amd._lib import BF16, F16, F32, ConvDesc, lib, ptr, stream
 from argus_amd.engine import _out, resnet50_blocks
 from argus_amd.models import NCameraCNN
 from argus_amd.utils import se3_exp
 
-SERVED = ("fp32", "bf16")
+SERVED = ("fp32", "bf16", "fp16")
+_DT = {"fp32": (F32, torch.float32), "bf16": (BF16, torch.bfloat16), "fp16": (F16, torch.float16)}
+F16_MAX = 65504.0  # the largest finite fp16: every fp16 store of the library saturates to it
 
 
 class _Conv:
@@ -42,14 +49,15 @@ class _Conv:
 class InferenceSession:
     """``session(images) -> (batch, 6)`` for a fixed ``batch`` and image size ``hw``.
 
-    ``compute_dtype``: "fp32" or "bf16" (default: the model's). ``graph``: capture the forward once per
+    ``compute_dtype``: "fp32", "bf16" or "fp16" (default: the model's; "fp16" only when asked for). ``graph``: capture the forward once per
     input dtype (fp32 / uint8) and replay it per call; False issues the same launches eagerly."""
 
     def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
                  graph: bool = True):
         dtype = model.compute_dtype if compute_dtype is None else compute_dtype
         if dtype not in SERVED:
-            raise ValueError(f"InferenceSession serves compute_dtype 'fp32' and 'bf16', got {dtype!r}")
+            raise ValueError(f"InferenceSession serves compute_dtype 'fp32' and 'bf16' (and 'fp16' when passed "
+                             f"explicitly), got {dtype!r}")
         p0 = next(model.parameters())
         if p0.device.type != "cuda":
             raise RuntimeError("argus_amd.InferenceSession runs only on the MI355X HIP path: move the model to a "
@@ -58,8 +66,7 @@ class InferenceSession:
         self.batch, self.hw, self.compute_dtype, self.graph = int(batch), (int(hw[0]), int(hw[1])), dtype, bool(graph)
         self.n_cams, self.rdim = model.n_cams, model.resnet_output_dim
         self.L = lib()
-        self.dt = BF16 if dtype == "bf16" else F32
-        self.tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
+        self.dt, self.tdt = _DT[dtype]
         self._graphs: dict = {}
         with torch.cuda.device(self.device):
             self._plan()
@@ -155,6 +162,8 @@ class InferenceSession:
                 L.conv_fold_bn(C.byref(cv.desc), dt, ptr(w), st, ptr(P[cv.bn + ".weight"]), ptr(P[cv.bn + ".bias"]),
                                ptr(Bf[cv.bn + ".running_mean"]), ptr(Bf[cv.bn + ".running_var"]),
                                C.c_float(eps[cv.bn]), ptr(cv.wf), ptr(cv.bias), s)
+            if self.compute_dtype == "fp16":
+                self._check_f16_range()
             for n in ("resnet.fc", "output_mlp.0", "output_mlp.2", "output_mlp.4"):
                 for k in ("weight", "bias"):
                     src = P[f"{n}.{k}"].detach()
@@ -167,13 +176,26 @@ class InferenceSession:
                                    for cv in self.convs.values())
                              + 4 * sum(t.numel() for t in self.head.values()))
 
+    def _check_f16_range(self) -> None:
+        """fp16 cannot hold a checkpoint whose folded weight overflows: the fold saturated it to +-65504 (or the
+        master was not finite). Say so here, once per refresh, not through a pose."""
+        for name, wf in [("resnet.conv1", self.stem_wf)] + [(cv.name, cv.wf) for cv in self.convs.values()]:
+            a = wf.abs().max().item()
+            if not a < F16_MAX:  # 65504 (saturated), inf or NaN
+                raise ValueError(f"InferenceSession(compute_dtype='fp16'): the folded weight of {name} reaches "
+                                 f"{a} (fp16 holds magnitudes below {F16_MAX}); serve this checkpoint in 'bf16' "
+                                 f"or 'fp32'")
+
     # ------------------------------------------------------------------ forward
-    def _conv(self, cv: _Conv, x, out, res, relu: int, s) -> None:
+    def _conv(self, cv: _Conv, x, out, res, relu: int, s, probe=None) -> None:
         self.L.conv_infer(C.byref(cv.desc), self.dt, ptr(x), ptr(cv.wf), ptr(cv.bias), ptr(res), relu, ptr(out),
                           cv.splits, ptr(self.ws), self.ws.numel(), s)
+        if probe is not None:
+            probe(out, cv.desc.n * cv.desc.ho * cv.desc.wo * cv.desc.k)
 
-    def _forward(self, x: torch.Tensor) -> torch.Tensor:
-        """The launches of one forward from the contiguous (batch, 3*n_cams, H, W) tensor ``x`` into self.pred."""
+    def _forward(self, x: torch.Tensor, probe=None) -> torch.Tensor:
+        """The launches of one forward from the contiguous (batch, 3*n_cams, H, W) tensor ``x`` into self.pred.
+        ``probe(buffer, elements)``: called after every launch that writes a pool buffer (activation_peak)."""
         L, dt, s, N = self.L, self.dt, stream(), self.N
         H, W = self.hw
         if x.dtype == torch.uint8:
@@ -183,16 +205,20 @@ class InferenceSession:
         h, a1, a2, yd, out = self.pool
         H1, W1 = self.stem_hw
         L.conv_fwd(C.byref(self.stem_desc), dt, ptr(self.x0), ptr(self.stem_wf), ptr(a1), None, None, None, s)
+        if probe is not None:
+            probe(a1, N * H1 * W1 * 64)
         L.maxpool_fwd(dt, N, H1, W1, 64, ptr(a1), ptr(self.stem_coef[0]), ptr(self.stem_coef[1]), ptr(h),
                       ptr(self.amax), s)
+        if probe is not None:
+            probe(h, N * self.pool_hw[0] * self.pool_hw[1] * 64)
         for c1, c2, c3, ds in self.schedule:
-            self._conv(c1, h, a1, None, 1, s)
-            self._conv(c2, a1, a2, None, 1, s)
+            self._conv(c1, h, a1, None, 1, s, probe)
+            self._conv(c2, a1, a2, None, 1, s, probe)
             res = h
             if ds is not None:
-                self._conv(ds, h, yd, None, 0, s)
+                self._conv(ds, h, yd, None, 0, s, probe)
                 res = yd
-            self._conv(c3, a2, out, res, 1, s)
+            self._conv(c3, a2, out, res, 1, s, probe)
             h, out = out, h
         hf, wf = self.final_hw
         L.avgpool_fwd(dt, N, hf * wf, 2048, ptr(h), ptr(self.feat), s)
@@ -239,6 +265,22 @@ class InferenceSession:
                 g = self._graphs[images.dtype] = self._capture(images.dtype)
             g.replay()
             return self.pred.clone()
+
+    def activation_peak(self, images: torch.Tensor) -> float:
+        """The largest |activation| one forward of ``images`` writes to any activation buffer (stem output,
+        max-pool output, every conv output), from one eager forward outside the graph. A diagnostic, not the
+        hot path: in fp16 it shows the headroom under 65504 (a saturated activation reads exactly 65504)."""
+        want = (self.batch, 3 * self.n_cams, *self.hw)
+        if not isinstance(images, torch.Tensor) or tuple(images.shape) != want or images.dtype not in self.static_in:
+            raise ValueError(f"InferenceSession.activation_peak expects float32 or uint8 images of shape {want}")
+        peak = torch.zeros((), dtype=torch.float32, device=self.device)
+
+        def probe(buf, elements):
+            torch.maximum(peak, buf[:elements].abs().max().float(), out=peak)
+
+        with torch.cuda.device(self.device), torch.no_grad():
+            self._forward(images.to(self.device).contiguous(), probe)
+        return float(peak.item())
 
     def pose(self, images: torch.Tensor) -> torch.Tensor:
         """(batch, 7) [t, qx, qy, qz, qw]: ``utils.se3_exp`` of the prediction, as ``get_pose``."""

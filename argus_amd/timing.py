@@ -1,7 +1,7 @@
 """Forward-latency benchmark — the MI355X counterpart of the reference's ``scripts/timing.py``.
 
     python -m argus_amd.timing [--trials 100] [--batch 2] [--hw 256 256] [--dtype fp32|bf16x3|bf16]
-                               [--eval] [--no-graph] [--frozen]
+                               [--eval] [--no-graph] [--frozen [--dtype fp16]]
     python -m argus_amd.timing --input-grad [--out profiles/input_grad.txt]
 
 Reference semantics (scripts/timing.py:10-48): ``NCameraCNN(n_cams=2)`` in fp32 on the GPU, left in
@@ -16,6 +16,7 @@ copied into the graph's static input buffer; ``--no-graph`` times eager launches
 
 ``--frozen`` times an ``argus_amd.infer.InferenceSession`` built from the model in eval mode instead (BN
 folded into the conv weights, one launch per conv, its own captured graph): the deployment path.
+``--dtype fp16`` exists only with ``--frozen``: the session runs in fp16 on an fp32 model.
 
 ``--input-grad`` measures the image gradient instead (``input_grad_table``): the stem data-gradient kernel
 alone against MIOpen's, and the train step with and without ``image_grad``.
@@ -38,10 +39,13 @@ from argus_amd.utils import time_torch_fn
 def forward_latency(trials: int = 100, batch: int = 2, hw=(256, 256), dtype: str = "fp32", train_mode: bool = True,
                     graph: bool = True, device: str = "cuda", frozen: bool = False) -> dict:
     """Mean / median / min seconds of one NCameraCNN forward (no_grad) over ``trials`` timed trials.
-    ``frozen``: the forward of an InferenceSession of the model in eval mode."""
+    ``frozen``: the forward of an InferenceSession of the model in eval mode, in compute dtype ``dtype``
+    ("fp16" is a session dtype only: the model behind it is fp32)."""
+    if dtype == "fp16" and not frozen:
+        raise ValueError("dtype 'fp16' is served by the frozen session only (frozen=True)")
     torch.manual_seed(0)
     cfg = NCameraCNNConfig(n_cams=2)
-    model = NCameraCNN(cfg, compute_dtype=dtype).to(device)
+    model = NCameraCNN(cfg, compute_dtype="fp32" if dtype == "fp16" else dtype).to(device)
     model.train(train_mode)
     H, W = hw
     static_x = torch.rand((batch, cfg.n_cams * 3, H, W), device=device)
@@ -49,7 +53,7 @@ def forward_latency(trials: int = 100, batch: int = 2, hw=(256, 256), dtype: str
     if frozen:
         from argus_amd.infer import InferenceSession
 
-        session = InferenceSession(model.eval(), batch, (H, W), graph=graph)
+        session = InferenceSession(model.eval(), batch, (H, W), compute_dtype=dtype, graph=graph)
         train_mode = False
 
         def run(x):
@@ -205,7 +209,7 @@ def input_grad_table(rounds: int = 3, samples: int = 20, device: str = "cuda") -
     return lines
 
 
-def main() -> None:
+def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--input-grad", action="store_true",
                     help="measure the image-gradient kernel and the step with image_grad (writes --out)")
@@ -213,12 +217,15 @@ def main() -> None:
     ap.add_argument("--trials", type=int, default=100)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--hw", type=int, nargs=2, default=(256, 256))
-    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16x3", "bf16"])
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16x3", "bf16", "fp16"],
+                    help="fp16: with --frozen only")
     ap.add_argument("--eval", action="store_true", help="eval-mode BN (running statistics)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a replayed hipGraph")
     ap.add_argument("--frozen", action="store_true",
-                    help="time an InferenceSession of the eval-mode model (fp32 / bf16)")
-    a = ap.parse_args()
+                    help="time an InferenceSession of the eval-mode model (fp32 / bf16 / fp16)")
+    a = ap.parse_args(argv)
+    if a.dtype == "fp16" and not a.frozen:
+        ap.error("--dtype fp16 is served by --frozen only")
     if a.input_grad:
         lines = input_grad_table()
         with open(a.out, "w") as f:

@@ -13,11 +13,17 @@ Not reproduced: the matplotlib pose plots and image dumps of validate.py:130-190
 out of scope) and the kornia photometric augmentations (the reference applies them only when
 ``use_train``; argus_amd.data warns about them). Batching (``batch_size`` > 1) gives the same
 per-example losses, since eval-mode BN is per-sample.
+
+``session_dtype`` (``--session-dtype fp32|bf16|fp16``, an extension): the predictions come from an
+``argus_amd.infer.InferenceSession`` of that compute dtype instead of ``model.eval()``, so a checkpoint's
+validation loss can be read at the precision it will be deployed in. A session has a fixed batch: the last
+short batch is padded by repeating its final sample and the padding rows are dropped.
 """
 from __future__ import annotations
 
 import os
 from dataclasses import dataclass, field
+from typing import Optional
 
 import torch
 from torch.utils.data import DataLoader
@@ -42,6 +48,7 @@ class ValConfig:
     use_train: bool = False
     device: str = field(default_factory=_default_device)
     batch_size: int = 1  # extension: the reference validates one example at a time
+    session_dtype: Optional[str] = None  # extension: "fp32" | "bf16" | "fp16" = predict with an InferenceSession
 
     def __post_init__(self) -> None:
         assert self.dataset_config is not None, "The dataset config must be provided with a valid dataset path!"
@@ -67,11 +74,24 @@ def validate(cfg: ValConfig) -> list[float]:
     dataset = CameraCubePoseDataset(cfg.dataset_config, cfg_aug=cfg.aug_config, train=cfg.use_train, uint8=True)
     loader = DataLoader(dataset, batch_size=cfg.batch_size, shuffle=False)
     losses: list[float] = []
+    session = None
     with torch.no_grad():
         for example in loader:
             images = example["images"].to(cfg.device)
             target = example["cube_pose"].to(cfg.device).to(torch.float32)
-            per = geometric_loss_fn(model(images), target)
+            if cfg.session_dtype is None:
+                pred = model(images)
+            else:
+                if session is None:  # the first batch is a full one and fixes the session's shape
+                    from argus_amd.infer import InferenceSession
+
+                    session = InferenceSession(model, images.shape[0], tuple(images.shape[-2:]),
+                                               compute_dtype=cfg.session_dtype)
+                n = images.shape[0]
+                if n < session.batch:  # the short tail: repeat its last sample, drop those rows again
+                    images = torch.cat([images, images[-1:].expand(session.batch - n, *images.shape[1:])])
+                pred = session(images.contiguous())[:n]
+            per = geometric_loss_fn(pred, target)
             losses.extend(per.reshape(-1).cpu().tolist())
     return losses
 
@@ -86,10 +106,13 @@ def main(argv=None) -> list[float]:
     ap.add_argument("--use-train", action=argparse.BooleanOptionalAction, default=False)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--batch-size", type=int, default=1)
+    ap.add_argument("--session-dtype", default=None, choices=["fp32", "bf16", "fp16"],
+                    help="predict with an InferenceSession of this compute dtype (default: model.eval())")
     a = ap.parse_args(argv)
     cfg = ValConfig(model_path=a.model_path,
                     dataset_config=CameraCubePoseDatasetConfig(a.dataset_path, center_crop=tuple(a.center_crop)),
-                    use_train=a.use_train, device=a.device, batch_size=a.batch_size)
+                    use_train=a.use_train, device=a.device, batch_size=a.batch_size,
+                    session_dtype=a.session_dtype)
     losses = validate(cfg)
     print(f"{len(losses)} examples, mean loss {sum(losses) / max(1, len(losses)):.6f}")
     return losses

@@ -8,7 +8,8 @@
  * (argus_amd/_lib.py, ctypes) binds exactly these symbols; INTEGRATION.md shows the binding.
  *
  * Conventions
- *  - Activations are NHWC, channel-contiguous, dtype ARGUS_F32 or ARGUS_BF16.
+ *  - Activations are NHWC, channel-contiguous, dtype ARGUS_F32 or ARGUS_BF16 (frozen inference also
+ *    ARGUS_F16, below).
  *  - Conv weights are OHWI ("KRSC"): w[k][r][s][c]. The stem (7x7, C=3) uses a padded compute layout
  *    w[k][r(8)][s(8)][c(4)] (r=7, s=7, c=3 zero) and an NHWC4 input (channel 3 zero).
  *  - Statistics, losses, gradients of parameters and optimizer state are fp32.
@@ -35,7 +36,18 @@ typedef void* argus_stream_t; /* hipStream_t */
  * weights are the pre-quantized copies argus_conv_weight_prep(_batch) writes with ARGUS_FP8 (e4m3 rows
  * [rows][cols] then scales [rows][cols/32], in the bf16 copy's buffer). The other passes and every
  * non-conv entry point (pass ARGUS_BF16) run bf16. */
-enum { ARGUS_F32 = 0, ARGUS_BF16 = 1, ARGUS_FP8 = 2 };
+/* ARGUS_F16 (frozen inference only): IEEE binary16 tensors, NHWC, 8 elements per 16-byte chunk like bf16;
+ * v_mfma_f32_16x16x32_f16 with fp32 accumulation; every store rounds to nearest even and saturates to
+ * +-65504 (NaN stays NaN). Served by the entry points of a frozen forward and no others:
+ *   argus_images_to_nhwc4, argus_images_u8_to_nhwc4,
+ *   argus_conv_weight_prep (stem descriptor only: writes w_fwd, ignores w_dgrad),
+ *   argus_conv_fwd (stem descriptor only, scale = shift = stat_part = NULL),
+ *   argus_maxpool_fwd, argus_avgpool_fwd, argus_conv_fold_bn,
+ *   argus_conv_infer, argus_conv_infer_splits, _max_splits, _workspace_bytes.
+ * Every other entry point that takes a dtype rejects it before anything is launched: the launching ones
+ * return ARGUS_ERR_ARG, the planning queries their "not served" value (0, or -1 where that is their error),
+ * and argus_last_error() names the dtype. There is no fp16 training path. */
+enum { ARGUS_F32 = 0, ARGUS_BF16 = 1, ARGUS_FP8 = 2, ARGUS_F16 = 3 };
 enum { ARGUS_OK = 0, ARGUS_ERR_ARG = 1, ARGUS_ERR_SHAPE = 2, ARGUS_ERR_HIP = 3 };
 
 /* One override of the kernel-selection policy (keys: argus_conv_policy_default). */
@@ -125,7 +137,7 @@ int argus_conv_fwd_bn_out(const argus_conv_desc* d, int dtype, const void* x, co
  * A deployed model's convolutions: eval-mode BatchNorm folded into the weights once, then one launch per
  * conv. Together they replace nn.Conv2d + nn.BatchNorm2d.eval() [+ add] + nn.ReLU of torchvision's
  * Bottleneck.forward (argus/models.py:43). Served: 1x1 (pad 0) and 3x3 (pad 1) convs of stride 1 or 2, c
- * and k multiples of 64, any h x w, dtype ARGUS_F32 or ARGUS_BF16 (anything else: ARGUS_ERR_ARG); not the
+ * and k multiples of 64, any h x w, dtype ARGUS_F32, ARGUS_BF16 or ARGUS_F16 (anything else: ARGUS_ERR_ARG); not the
  * stem, which keeps argus_conv_fwd + argus_maxpool_fwd with argus_bn_eval_coeffs. Nothing here allocates
  * or synchronises: every call can be captured into a graph.
  *
@@ -138,8 +150,8 @@ int argus_conv_fold_bn(const argus_conv_desc* d, int dtype, const float* w_maste
                        float eps, void* w_fold, float* bias, argus_stream_t stream);
 /* The reduction (r*s*c) of argus_conv_infer may be split over workgroups when its output tiles alone
  * leave the chip idle. _splits: the library's choice for this shape (>= 1; 0 = shape / dtype not
- * served); _max_splits: the largest accepted value = the k-steps of the reduction (r*s*c / 64 in bf16,
- * / 32 in fp32); _workspace_bytes: what `splits` slices need (0 for splits <= 1): one uint32 ticket per
+ * served); _max_splits: the largest accepted value = the k-steps of the reduction (r*s*c / 64 in bf16
+ * and fp16, / 32 in fp32); _workspace_bytes: what `splits` slices need (0 for splits <= 1): one uint32 ticket per
  * output tile at the start of the workspace (padded to 256 bytes), then the fp32 slabs. */
 int argus_conv_infer_splits(const argus_conv_desc* d, int dtype);
 int argus_conv_infer_max_splits(const argus_conv_desc* d, int dtype);
