@@ -102,6 +102,9 @@ SIGNATURES = {
     "argus_conv_infer_max_splits": (_I, [_DESC, _I]),
     "argus_conv_infer_workspace_bytes": (_SZ, [_DESC, _I, _I]),
     "argus_conv_infer": (_I, [_DESC, _I, _P, _P, _P, _P, _I, _P, _I, _P, _SZ, _P]),
+    "argus_conv_fold_bn_dgrad": (_I, [_DESC, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
+    "argus_conv_infer_dgrad_plan": (_I, [_DESC, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_SZ)]),
+    "argus_conv_infer_dgrad": (_I, [_DESC, _I, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
     "argus_conv_x8_ok": (_I, [_DESC, _I]),
     "argus_conv_fwd_stats_only_rows": (_I, [_DESC, _I]),
     "argus_conv_fwd_stats_only_tile": (_I, [_DESC, _I]),
@@ -151,6 +154,7 @@ SIGNATURES = {
                                       _P, _P, _P]),
     "argus_avgpool_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P]),
     "argus_avgpool_bwd": (_I, [_I, _I, _I, _I, _P, _P, _P]),
+    "argus_avgpool_bwd_relu": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "argus_gemm_f32_workspace_bytes": (_SZ, [_I, _I, _I]),
     "argus_augment_params_bytes": (_SZ, []),
     "argus_augment_scratch_bytes": (_SZ, [_I64, _I, _I]),

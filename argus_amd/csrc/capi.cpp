@@ -167,6 +167,37 @@ int argus_conv_infer(const argus_conv_desc* d, int dtype, const void* x, const v
                     (hipStream_t)stream);
 }
 
+int argus_conv_fold_bn_dgrad(const argus_conv_desc* d, int dtype, const float* w_master, const int64_t* strides,
+                             const float* gamma, const float* beta, const float* running_mean,
+                             const float* running_var, float eps, void* w_fold_dgrad, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_fold_bn_dgrad")) return ARGUS_ERR_ARG;
+  if (!d || !w_master || !gamma || !beta || !running_mean || !running_var || !w_fold_dgrad) {
+    set_error("conv_fold_bn_dgrad: null argument");
+    return ARGUS_ERR_ARG;
+  }
+  return conv_fold_bn_dgrad(*d, dtype, w_master, strides, gamma, beta, running_mean, running_var, eps, w_fold_dgrad,
+                            (hipStream_t)stream);
+}
+
+int argus_conv_infer_dgrad_plan(const argus_conv_desc* d, int dtype, int splits_in, int* splits, int* max_splits,
+                                size_t* workspace_bytes) {
+  if (f16_unserved(dtype, "conv_infer_dgrad_plan")) return ARGUS_ERR_ARG;
+  if (!d || !splits || !max_splits || !workspace_bytes) {
+    set_error("conv_infer_dgrad_plan: null argument");
+    return ARGUS_ERR_ARG;
+  }
+  return conv_infer_dgrad_plan(*d, dtype, splits_in, splits, max_splits, workspace_bytes);
+}
+
+int argus_conv_infer_dgrad(const argus_conv_desc* d, int dtype, const void* dy, const void* w_fold_dgrad,
+                           const void* addend, const void* mask_src, void* dx, int splits, void* workspace,
+                           size_t workspace_bytes, argus_stream_t stream) {
+  if (f16_unserved(dtype, "conv_infer_dgrad")) return ARGUS_ERR_ARG;
+  if (!d || !dy || !w_fold_dgrad || !dx) { set_error("conv_infer_dgrad: null argument"); return ARGUS_ERR_ARG; }
+  return conv_infer_dgrad(*d, dtype, dy, w_fold_dgrad, addend, mask_src, dx, splits, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
 int argus_conv_policy_default(int key) { return policy_default(key); }
 
 int argus_conv_launch_info(const argus_conv_desc* d, int dtype, int pass, int64_t* flops) {

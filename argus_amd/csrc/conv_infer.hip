@@ -336,12 +336,16 @@ static int infer_check(const argus_conv_desc& d, int dtype, const char* who) {
 static int infer_bke(int dtype) { return infer_16bit(dtype) ? 64 : 32; }
 static int infer_nk(const argus_conv_desc& d, int dtype) { return d.r * d.s * d.c / infer_bke(dtype); }
 // 32-row tiles while 64-row tiles would not give every CU one
-static int infer_bm(const argus_conv_desc& d) {
+int infer_bm(const argus_conv_desc& d) {
   const int M = d.n * d.ho * d.wo;
   return cdiv(M, 64) * (d.k / kInferBN) >= kInferCUs ? 64 : 32;
 }
-static int infer_tiles(const argus_conv_desc& d) { return cdiv(d.n * d.ho * d.wo, infer_bm(d)) * (d.k / kInferBN); }
-static size_t infer_ticket_bytes(const argus_conv_desc& d) { return ((size_t)infer_tiles(d) * 4 + 255) / 256 * 256; }
+int infer_tiles(const argus_conv_desc& d) { return cdiv(d.n * d.ho * d.wo, infer_bm(d)) * (d.k / kInferBN); }
+// One workspace serves every conv of a session: the ticket words of one launch must never be the slab bytes of
+// another, so the ticket region has one size (4 KB: 1024 tiles) for every shape the split rule below can choose
+// (tiles * splits <= 256); only a caller-forced split of a larger grid grows it. (Padded to 256 bytes per shape, a
+// 65..128-tile conv found the slabs of a <= 64-tile conv in its tickets 64.. from the second forward on.)
+size_t infer_ticket_bytes(const argus_conv_desc& d) { return ((size_t)infer_tiles(d) * 4 + 4095) / 4096 * 4096; }
 
 int conv_infer_max_splits(const argus_conv_desc& d, int dtype) {
   return infer_check(d, dtype, "conv_infer_max_splits") ? 0 : infer_nk(d, dtype);

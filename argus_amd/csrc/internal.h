@@ -121,6 +121,17 @@ int conv_infer_max_splits(const argus_conv_desc& d, int dtype);
 size_t conv_infer_ws_bytes(const argus_conv_desc& d, int dtype, int splits);
 int conv_infer(const argus_conv_desc& d, int dtype, const void* x, const void* w, const float* bias, const void* res,
                int relu, void* out, int splits, void* ws, size_t ws_bytes, hipStream_t st);
+// the forward's tiling of a served descriptor: rows per tile, output tiles, bytes of ticket words
+int infer_bm(const argus_conv_desc& d);
+int infer_tiles(const argus_conv_desc& d);
+size_t infer_ticket_bytes(const argus_conv_desc& d);
+// frozen gradient (conv_infer_bwd.hip): the folded weights in data-gradient layout, the plan, the data gradient
+int conv_fold_bn_dgrad(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides, const float* gamma,
+                       const float* beta, const float* rm, const float* rv, float eps, void* wfd, hipStream_t st);
+int conv_infer_dgrad_plan(const argus_conv_desc& d, int dtype, int splits_in, int* splits, int* max_splits,
+                          size_t* ws_bytes);
+int conv_infer_dgrad(const argus_conv_desc& d, int dtype, const void* dy, const void* wfd, const void* addend,
+                     const void* mask_src, void* dx, int splits, void* ws, size_t ws_bytes, hipStream_t st);
 int images_to_nhwc4(int dtype, int64_t nimg, int h, int w, const float* x, void* out,
                     hipStream_t st);
 int images_u8_to_nhwc4(int dtype, int64_t nimg, int h, int w, const uint8_t* x, void* out,

@@ -220,6 +220,11 @@ class InferenceSession:
                 res = yd
             self._conv(c3, a2, out, res, 1, s, probe)
             h, out = out, h
+        return self._head(h)
+
+    def _head(self, h: torch.Tensor) -> torch.Tensor:
+        """Average pool of the last block's output ``h``, fc, GELU and the MLP into self.pred (fp32)."""
+        L, dt, s, N = self.L, self.dt, stream(), self.N
         hf, wf = self.final_hw
         L.avgpool_fwd(dt, N, hf * wf, 2048, ptr(h), ptr(self.feat), s)
         B, D, R = self.batch, self.n_cams * self.rdim, self.rdim

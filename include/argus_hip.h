@@ -152,7 +152,9 @@ int argus_conv_fold_bn(const argus_conv_desc* d, int dtype, const float* w_maste
  * leave the chip idle. _splits: the library's choice for this shape (>= 1; 0 = shape / dtype not
  * served); _max_splits: the largest accepted value = the k-steps of the reduction (r*s*c / 64 in bf16
  * and fp16, / 32 in fp32); _workspace_bytes: what `splits` slices need (0 for splits <= 1): one uint32 ticket per
- * output tile at the start of the workspace (padded to 256 bytes), then the fp32 slabs. */
+ * output tile at the start of the workspace (padded to a multiple of 4096 bytes: up to 1024 tiles, and so
+ * every shape the library splits on its own, has its slabs at the same offset, which is what lets one
+ * workspace serve convs of different tile counts one after another), then the fp32 slabs. */
 int argus_conv_infer_splits(const argus_conv_desc* d, int dtype);
 int argus_conv_infer_max_splits(const argus_conv_desc* d, int dtype);
 size_t argus_conv_infer_workspace_bytes(const argus_conv_desc* d, int dtype, int splits);
@@ -166,6 +168,39 @@ size_t argus_conv_infer_workspace_bytes(const argus_conv_desc* d, int dtype, int
 int argus_conv_infer(const argus_conv_desc* d, int dtype, const void* x, const void* w_fold, const float* bias,
                      const void* res, int relu, void* out, int splits, void* workspace, size_t workspace_bytes,
                      argus_stream_t stream);
+/* ---- frozen gradient (ABI 21, added without a version change: detect by symbol) -----------------
+ * The input gradient of the folded network: what torch.autograd.grad gives through nn.Conv2d +
+ * nn.BatchNorm2d.eval() + nn.ReLU of torchvision's Bottleneck.forward with the model in eval mode
+ * (argus/models.py:66-90 under torch.autograd.grad after model.eval()). With BN folded the network is
+ * conv + bias + ReLU, so its backward is one data-gradient GEMM per conv over the same folded weights, the
+ * producer's ReLU derivative applied in the epilogue. `d` is always the forward conv's descriptor, of the
+ * four kinds argus_conv_infer serves; dtype ARGUS_F32 or ARGUS_BF16 (ARGUS_F16, ARGUS_FP8 and unknown
+ * values: ARGUS_ERR_ARG, "dtype" in the message; there is no fp16 gradient). No weight gradients. Nothing
+ * here allocates or synchronises: every call can be captured into a graph.
+ *
+ * argus_conv_fold_bn_dgrad: argus_conv_fold_bn's inputs; w_fold_dgrad[c][r'][s'][k] = T(w[k][c][r][s] *
+ * scale[k]) with r' = R-1-r, s' = S-1-s: the transposed, 180-degree-rotated filter, [C][R*S*K], each element
+ * the same single fp32 multiply and rounding as argus_conv_fold_bn's (the two copies hold identical values
+ * in different places). */
+int argus_conv_fold_bn_dgrad(const argus_conv_desc* d, int dtype, const float* w_master, const int64_t* strides,
+                             const float* gamma, const float* beta, const float* running_mean,
+                             const float* running_var, float eps, void* w_fold_dgrad, argus_stream_t stream);
+/* Plan of argus_conv_infer_dgrad for `d`: *splits = splits_in, or the library's choice when splits_in == 0
+ * (argus_conv_infer_splits' cost model on the mirrored problem: n*h*w rows, c columns, r*s*k reduction);
+ * *max_splits = the k-steps of the reduction (r*s*k / 64 in bf16, / 32 in fp32); *workspace_bytes = what
+ * *splits slices need (0 for <= 1), laid out as argus_conv_infer's. splits_in outside 0..max: ARGUS_ERR_ARG. */
+int argus_conv_infer_dgrad_plan(const argus_conv_desc* d, int dtype, int splits_in, int* splits, int* max_splits,
+                                size_t* workspace_bytes);
+/* dx = (mask_src > 0 ? 1 : 0) * (conv_transpose(dy, w) + addend): dy (n, ho, wo, k); dx, addend (may be
+ * NULL) and mask_src (may be NULL: no mask) (n, h, w, c), all NHWC in dtype; the sum is made in fp32 and
+ * rounded once. mask_src is the conv's own input activation, the post-ReLU output of its producer: the
+ * epilogue applies that ReLU's derivative (> 0, so 0 and NaN mask to 0). Every element of dx is written,
+ * the pixels a stride-2 conv never reads included (their conv_transpose term is 0). splits / workspace
+ * exactly as argus_conv_infer (same ticket protocol, the tickets zero on entry and on return, bitwise
+ * reproducible for a given `splits`). */
+int argus_conv_infer_dgrad(const argus_conv_desc* d, int dtype, const void* dy, const void* w_fold_dgrad,
+                           const void* addend, const void* mask_src, void* dx, int splits, void* workspace,
+                           size_t workspace_bytes, argus_stream_t stream);
 
 int argus_conv_fwd_stat_rows(const argus_conv_desc* d, int dtype);
 int argus_conv_fwd_stat_tile(const argus_conv_desc* d, int dtype);
@@ -499,6 +534,11 @@ int argus_avgpool_fwd(int dtype, int n, int hw, int c, const void* x, float* fea
                       argus_stream_t stream);
 int argus_avgpool_bwd(int dtype, int n, int hw, int c, const float* dfeat, void* dx,
                       argus_stream_t stream);
+/* argus_avgpool_bwd through the ReLU that produced the pooled tensor: dx = dfeat/hw * (out > 0), `out` the
+ * (n, hw, c) post-ReLU activation in dtype (the last Bottleneck's output under torch.autograd.grad in eval
+ * mode, argus/models.py:66-90). ARGUS_F32 or ARGUS_BF16. */
+int argus_avgpool_bwd_relu(int dtype, int n, int hw, int c, const float* dfeat, const void* out, void* dx,
+                           argus_stream_t stream);
 
 /* ---- FC / MLP head (nn.Linear + exact GELU; models.py:56-64,88), fp32 ------------------------ */
 /* C[m][n] = sum_k opA(A)[m][k] * opB(B)[k][n]; opA(A)[m][k] = trans_a ? A[k*lda+m] : A[m*lda+k],
