@@ -35,34 +35,8 @@ static int reduce_groups(int rows) {
 // reducer's agent-scope acquire precedes its plain loads (cdna_hip_programming.md §6 Guideline 16,
 // counter form with sc1 stores; correct for any workgroup -> XCD placement). The reducer resets cnt[x], so the
 // counters stay zero between calls; they are zeroed once when the workspace is allocated.
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) unsigned gu32;
-
-// a group result, stored write-through (sc1: two 8-byte agent-scope atomic stores), so publishing it
-// needs no L2 write-back (release) fence — only the drain in ticket_last
-ARGUS_DEV void store_wt(double2* p, double2 v) {
-  gu64* q = (gu64*)p;
-  __hip_atomic_store(q, (unsigned long long)__double_as_longlong(v.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(q + 1, (unsigned long long)__double_as_longlong(v.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-ARGUS_DEV bool ticket_last(unsigned* cnt_, int G, int* flag) {
-  gu32* cnt = (gu32*)cnt_;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its sc1 stores
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned t = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = t == (unsigned)(G - 1);
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    *flag = last;
-  }
-  __syncthreads();
-  return *flag != 0;
-}
+// The ticket and the write-through group-result store are bnfin.h's (fin_ticket<kWriteThrough>, store_wt2:
+// sc1 stores need no L2 write-back (release) fence, only the drain in fin_ticket).
 
 // fixed-order sum over the G group results of this block's 64 channels: kFinLanes row lanes, then the lanes in order
 // Finalize blocks: 64 channels x kFinLanes row lanes. 16 lanes (1024 threads: one batch of loads per
@@ -143,9 +117,9 @@ __global__ __launch_bounds__(64 * kFinLanes) void stats_finalize_kernel(const Bn
   if (lane_r == 0 && c < a.C) {
     double2 t = red[0][threadIdx.x];
     for (int i = 1; i < kFinLanes; ++i) { t.x += red[i][threadIdx.x].x; t.y += red[i][threadIdx.x].y; }
-    store_wt(a.red + (size_t)g * a.C + c, t);
+    store_wt2(a.red + (size_t)g * a.C + c, t);
   }
-  if (!ticket_last(a.cnt + blockIdx.x, a.G, &flag)) return;
+  if (!fin_ticket<kWriteThrough>(a.cnt + blockIdx.x, (unsigned)a.G, &flag)) return;
   __syncthreads();
   const double2 tot = merge_groups(a.red, a.G, a.C, c, red);
   if (blockIdx.x == 0 && threadIdx.x == 0 && a.nbt) a.nbt[0] += 1;
@@ -429,9 +403,9 @@ __global__ __launch_bounds__(64 * kFinLanes) void bwd_finalize_kernel(const BnBw
   if (lane_r == 0 && c < a.C) {
     double2 t = red[0][threadIdx.x];
     for (int i = 1; i < kFinLanes; ++i) { t.x += red[i][threadIdx.x].x; t.y += red[i][threadIdx.x].y; }
-    store_wt(a.red + (size_t)g * a.C + c, t);
+    store_wt2(a.red + (size_t)g * a.C + c, t);
   }
-  if (!ticket_last(a.cnt + blockIdx.x, a.G, &flag)) return;
+  if (!fin_ticket<kWriteThrough>(a.cnt + blockIdx.x, (unsigned)a.G, &flag)) return;
   __syncthreads();
   const double2 tot = merge_groups(a.red, a.G, a.C, c, red);
   if (lane_r != 0 || c >= a.C) return;

@@ -45,12 +45,28 @@ ARGUS_DEV void bn_eval_coeff(const float* gamma, const float* beta, const float*
   shift = beta[c] - rm[c] * sc;
 }
 
-// Every thread of the workgroup calls this (uniform). True in the workgroup that drew ticket n-1.
+// The ticket hand-off, the only one in the library. Every thread of the workgroup calls this (uniform) after
+// its stores. True in the workgroup that drew ticket n-1, which also resets the counter for the next launch.
+// kWriteThrough: the producers stored with agent-scope atomic stores (store_part, store_wt2, store_count), so
+// the drain before the barrier publishes them and no release fence is needed (the BN finalizes).
+// kPlainStores: the producers stored plainly (the frozen convs' slabs, infer_gemm.h): every wave drains ->
+// workgroup barrier -> one lane: agent-scope release fence, a second drain (the fence's own wait may be
+// dropped: keep it), then the relaxed agent-scope fetch_add (MI355X_MICROARCH.md §Workgroup dispatch).
+// Both: the last arriver runs an agent-scope acquire fence + drain before the workgroup's plain loads.
+// Correct for any placement of the arriving workgroups. `flag` is an LDS word the caller may reuse once
+// every thread has returned (a caller that overwrites it at once needs a barrier of its own first).
+constexpr bool kWriteThrough = false, kPlainStores = true;
+
+template <bool kRelease>
 ARGUS_DEV bool fin_ticket(unsigned* cnt_, unsigned n, int* flag) {
   fin_gu32* cnt = (fin_gu32*)cnt_;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its write-through stores
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores
   __syncthreads();
   if (threadIdx.x == 0) {
+    if constexpr (kRelease) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     const unsigned t = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int last = t == n - 1;
     if (last) {
@@ -108,7 +124,7 @@ ARGUS_DEV void bn_fin_arrive(const BnFin& f, int t, int nt, double2* scratch, in
   const int g = t / f.gt;
   const int gsz = min(f.gt, f.T - g * f.gt);
   unsigned* cnt = f.cnt + (size_t)nt * (f.ng + 1);
-  if (!fin_ticket(cnt + g, (unsigned)gsz, flag)) return;
+  if (!fin_ticket<kWriteThrough>(cnt + g, (unsigned)gsz, flag)) return;
   const int cp = threadIdx.x % CP, lr = threadIdx.x / CP;
   const int c = nt * COLS + 2 * cp;
   const bool dual = f.part2 != nullptr;
@@ -150,7 +166,7 @@ ARGUS_DEV void bn_fin_arrive(const BnFin& f, int t, int nt, double2* scratch, in
     __syncthreads();
   }
   // level 2: the group results, fixed order
-  if (!fin_ticket(cnt + f.ng, (unsigned)f.ng, flag)) return;
+  if (!fin_ticket<kWriteThrough>(cnt + f.ng, (unsigned)f.ng, flag)) return;
 #pragma unroll
   for (int br = 0; br < 2; ++br) {
     if (br == 1 && !dual) break;
@@ -246,7 +262,7 @@ ARGUS_DEV void bn_fwd_fin_arrive(const BnFwdFin& f, int t, int nt, double2* scra
   const int g = t / f.gt;
   const int gsz = min(f.gt, f.T - g * f.gt);
   unsigned* cnt = f.cnt + (size_t)nt * (f.ng + 1);
-  if (!fin_ticket(cnt + g, (unsigned)gsz, flag)) return;
+  if (!fin_ticket<kWriteThrough>(cnt + g, (unsigned)gsz, flag)) return;
   const int cl = threadIdx.x % TC, lr = threadIdx.x / TC;  // lr < 4: the row lanes
   const int c = nt * COLS + cl * CPT;
   const bool act = lr < 4 && c < f.C;
@@ -304,7 +320,7 @@ ARGUS_DEV void bn_fwd_fin_arrive(const BnFwdFin& f, int t, int nt, double2* scra
   __syncthreads();
   // level 2: the G group slots in order (those past the ng groups with rows hold zeros in
   // stats_finalize_kernel: the masked +0.0 here)
-  if (!fin_ticket(cnt + f.ng, (unsigned)f.ng, flag)) return;
+  if (!fin_ticket<kWriteThrough>(cnt + f.ng, (unsigned)f.ng, flag)) return;
 #pragma unroll
   for (int k = 0; k < CPT; ++k) { S[k] = 0.0; Q[k] = 0.0; }
   if (act)

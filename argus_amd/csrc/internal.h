@@ -112,22 +112,24 @@ int conv_wgrad(const argus_conv_desc& d, int dtype, const void* x, const float* 
                hipStream_t st);
 int conv_weight_prep(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides,
                      void* wf, void* wd, hipStream_t st);
-// frozen inference (conv_infer.hip): BN fold, split choice / bound / workspace, forward
+// frozen inference (conv_infer.hip): both BN folds, split choice / bound / workspace, forward
 int conv_fold_bn(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides, const float* gamma,
                  const float* beta, const float* rm, const float* rv, float eps, void* wf, float* bias,
                  hipStream_t st);
+int conv_fold_bn_dgrad(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides, const float* gamma,
+                       const float* beta, const float* rm, const float* rv, float eps, void* wfd, hipStream_t st);
 int conv_infer_splits(const argus_conv_desc& d, int dtype);
 int conv_infer_max_splits(const argus_conv_desc& d, int dtype);
 size_t conv_infer_ws_bytes(const argus_conv_desc& d, int dtype, int splits);
 int conv_infer(const argus_conv_desc& d, int dtype, const void* x, const void* w, const float* bias, const void* res,
                int relu, void* out, int splits, void* ws, size_t ws_bytes, hipStream_t st);
-// the forward's tiling of a served descriptor: rows per tile, output tiles, bytes of ticket words
+// what the frozen convs serve (ARGUS_OK, or an error with its message set; F16 only where serves_f16), and the
+// forward's tiling of a served descriptor: rows per tile, output tiles, bytes of ticket words
+int infer_check(const argus_conv_desc& d, int dtype, const char* who, bool serves_f16);
 int infer_bm(const argus_conv_desc& d);
 int infer_tiles(const argus_conv_desc& d);
 size_t infer_ticket_bytes(const argus_conv_desc& d);
-// frozen gradient (conv_infer_bwd.hip): the folded weights in data-gradient layout, the plan, the data gradient
-int conv_fold_bn_dgrad(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides, const float* gamma,
-                       const float* beta, const float* rm, const float* rv, float eps, void* wfd, hipStream_t st);
+// frozen gradient (conv_infer_bwd.hip): the plan, the data gradient
 int conv_infer_dgrad_plan(const argus_conv_desc& d, int dtype, int splits_in, int* splits, int* max_splits,
                           size_t* ws_bytes);
 int conv_infer_dgrad(const argus_conv_desc& d, int dtype, const void* dy, const void* wfd, const void* addend,

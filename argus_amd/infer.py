@@ -158,10 +158,9 @@ class InferenceSession:
                              C.c_float(eps["resnet.bn1"]), ptr(self.stem_coef[0]), ptr(self.stem_coef[1]), s)
             for cv in self.convs.values():
                 w = P[cv.name + ".weight"]
-                st = (C.c_int64 * 4)(*w.stride())
-                L.conv_fold_bn(C.byref(cv.desc), dt, ptr(w), st, ptr(P[cv.bn + ".weight"]), ptr(P[cv.bn + ".bias"]),
-                               ptr(Bf[cv.bn + ".running_mean"]), ptr(Bf[cv.bn + ".running_var"]),
-                               C.c_float(eps[cv.bn]), ptr(cv.wf), ptr(cv.bias), s)
+                self._fold(cv, (ptr(w), (C.c_int64 * 4)(*w.stride()), ptr(P[cv.bn + ".weight"]),
+                                ptr(P[cv.bn + ".bias"]), ptr(Bf[cv.bn + ".running_mean"]),
+                                ptr(Bf[cv.bn + ".running_var"]), C.c_float(eps[cv.bn])), s)
             if self.compute_dtype == "fp16":
                 self._check_f16_range()
             for n in ("resnet.fc", "output_mlp.0", "output_mlp.2", "output_mlp.4"):
@@ -175,6 +174,11 @@ class InferenceSession:
                              + sum(cv.wf.numel() * cv.wf.element_size() + 4 * cv.bias.numel()
                                    for cv in self.convs.values())
                              + 4 * sum(t.numel() for t in self.head.values()))
+
+    def _fold(self, cv: _Conv, master, s) -> None:
+        """Fold ``cv`` from ``master``: (weight, strides, gamma, beta, running mean, running var, eps), the
+        arguments every fold entry point takes between the dtype and its outputs."""
+        self.L.conv_fold_bn(C.byref(cv.desc), self.dt, *master, ptr(cv.wf), ptr(cv.bias), s)
 
     def _check_f16_range(self) -> None:
         """fp16 cannot hold a checkpoint whose folded weight overflows: the fold saturated it to +-65504 (or the
@@ -193,25 +197,35 @@ class InferenceSession:
         if probe is not None:
             probe(out, cv.desc.n * cv.desc.ho * cv.desc.wo * cv.desc.k)
 
+    def _buffers(self):
+        """Where a forward writes: the stem output, the max-pool output and per block (a1, a2, out, yd); a block's
+        ``out`` is the next block's input. Here: five rotating buffers, the stem output borrowing a1's."""
+        h, a1, a2, yd, out = self.pool
+        blocks = []
+        for _ in self.schedule:
+            blocks.append((a1, a2, out, yd))
+            h, out = out, h
+        return a1, self.pool[0], blocks
+
     def _forward(self, x: torch.Tensor, probe=None) -> torch.Tensor:
         """The launches of one forward from the contiguous (batch, 3*n_cams, H, W) tensor ``x`` into self.pred.
-        ``probe(buffer, elements)``: called after every launch that writes a pool buffer (activation_peak)."""
+        ``probe(buffer, elements)``: called after every launch that writes an activation (activation_peak)."""
         L, dt, s, N = self.L, self.dt, stream(), self.N
         H, W = self.hw
         if x.dtype == torch.uint8:
             L.images_u8_to_nhwc4(dt, N, H, W, ptr(x), ptr(self.x0), s)
         else:
             L.images_to_nhwc4(dt, N, H, W, ptr(x), ptr(self.x0), s)
-        h, a1, a2, yd, out = self.pool
+        y0, h, blocks = self._buffers()
         H1, W1 = self.stem_hw
-        L.conv_fwd(C.byref(self.stem_desc), dt, ptr(self.x0), ptr(self.stem_wf), ptr(a1), None, None, None, s)
+        L.conv_fwd(C.byref(self.stem_desc), dt, ptr(self.x0), ptr(self.stem_wf), ptr(y0), None, None, None, s)
         if probe is not None:
-            probe(a1, N * H1 * W1 * 64)
-        L.maxpool_fwd(dt, N, H1, W1, 64, ptr(a1), ptr(self.stem_coef[0]), ptr(self.stem_coef[1]), ptr(h),
+            probe(y0, N * H1 * W1 * 64)
+        L.maxpool_fwd(dt, N, H1, W1, 64, ptr(y0), ptr(self.stem_coef[0]), ptr(self.stem_coef[1]), ptr(h),
                       ptr(self.amax), s)
         if probe is not None:
             probe(h, N * self.pool_hw[0] * self.pool_hw[1] * 64)
-        for c1, c2, c3, ds in self.schedule:
+        for (c1, c2, c3, ds), (a1, a2, out, yd) in zip(self.schedule, blocks):
             self._conv(c1, h, a1, None, 1, s, probe)
             self._conv(c2, a1, a2, None, 1, s, probe)
             res = h
@@ -219,7 +233,7 @@ class InferenceSession:
                 self._conv(ds, h, yd, None, 0, s, probe)
                 res = yd
             self._conv(c3, a2, out, res, 1, s, probe)
-            h, out = out, h
+            h = out
         return self._head(h)
 
     def _head(self, h: torch.Tensor) -> torch.Tensor:
@@ -240,44 +254,47 @@ class InferenceSession:
                    ptr(hd["output_mlp.4", "bias"]), 1, None, ws, wsn, s)
         return self.pred
 
-    def _capture(self, dtype) -> torch.cuda.CUDAGraph:
-        x = self.static_in[dtype]
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # untimed warm-up outside the capture
-            self._forward(x)
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._forward(x)
-        return g
+    def _check_images(self, images, who: str) -> None:
+        want = (self.batch, 3 * self.n_cams, *self.hw)
+        name = f"{type(self).__name__}.{who}"
+        if not isinstance(images, torch.Tensor) or tuple(images.shape) != want:
+            raise ValueError(f"{name} expects images of shape {want}, got "
+                             f"{tuple(images.shape) if isinstance(images, torch.Tensor) else type(images).__name__}")
+        if images.dtype not in self.static_in:
+            raise ValueError(f"{name} expects float32 or uint8 images, got {images.dtype}")
+
+    def _run(self, kind: str, images: torch.Tensor, body) -> None:
+        """``body(x)`` eagerly on ``images``, or captured once per (kind, input dtype) and replayed."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            if not self.graph:
+                body(images.to(self.device).contiguous())
+                return
+            x = self.static_in[images.dtype]
+            x.copy_(images)
+            g = self._graphs.get((kind, images.dtype))
+            if g is None:
+                side = torch.cuda.Stream(self.device)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):  # untimed warm-up outside the capture
+                    body(x)
+                torch.cuda.current_stream().wait_stream(side)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    body(x)
+                self._graphs[kind, images.dtype] = g
+            g.replay()
 
     def __call__(self, images: torch.Tensor) -> torch.Tensor:
         """(batch, 3*n_cams, H, W) fp32 images in [0, 1] or uint8 in [0, 255] -> (batch, 6) se(3), a fresh tensor."""
-        want = (self.batch, 3 * self.n_cams, *self.hw)
-        if not isinstance(images, torch.Tensor) or tuple(images.shape) != want:
-            raise ValueError(f"InferenceSession expects images of shape {want}, got "
-                             f"{tuple(images.shape) if isinstance(images, torch.Tensor) else type(images).__name__}")
-        if images.dtype not in self.static_in:
-            raise ValueError(f"InferenceSession expects float32 or uint8 images, got {images.dtype}")
-        with torch.cuda.device(self.device), torch.no_grad():
-            if not self.graph:
-                x = images.to(self.device).contiguous()
-                return self._forward(x).clone()
-            self.static_in[images.dtype].copy_(images)
-            g = self._graphs.get(images.dtype)
-            if g is None:
-                g = self._graphs[images.dtype] = self._capture(images.dtype)
-            g.replay()
-            return self.pred.clone()
+        self._check_images(images, "__call__")
+        self._run("forward", images, self._forward)
+        return self.pred.clone()
 
     def activation_peak(self, images: torch.Tensor) -> float:
         """The largest |activation| one forward of ``images`` writes to any activation buffer (stem output,
         max-pool output, every conv output), from one eager forward outside the graph. A diagnostic, not the
         hot path: in fp16 it shows the headroom under 65504 (a saturated activation reads exactly 65504)."""
-        want = (self.batch, 3 * self.n_cams, *self.hw)
-        if not isinstance(images, torch.Tensor) or tuple(images.shape) != want or images.dtype not in self.static_in:
-            raise ValueError(f"InferenceSession.activation_peak expects float32 or uint8 images of shape {want}")
+        self._check_images(images, "activation_peak")
         peak = torch.zeros((), dtype=torch.float32, device=self.device)
 
         def probe(buf, elements):

@@ -100,48 +100,15 @@ class GradientSession(InferenceSession):
     def refresh(self) -> None:
         """Re-fold both weight copies from the model's current parameters and buffers (never writes the model)."""
         super().refresh()
-        L, dt = self.L, self.dt
-        with torch.cuda.device(self.device), torch.no_grad():
-            s = stream()
-            P = dict(self.model.named_parameters())
-            Bf = dict(self.model.named_buffers())
-            eps = {n: m.eps for n, m in self.model.named_modules() if isinstance(m, torch.nn.BatchNorm2d)}
-            for cv in self.convs.values():
-                w = P[cv.name + ".weight"]
-                st = (C.c_int64 * 4)(*w.stride())
-                L.conv_fold_bn_dgrad(C.byref(cv.desc), dt, ptr(w), st, ptr(P[cv.bn + ".weight"]),
-                                     ptr(P[cv.bn + ".bias"]), ptr(Bf[cv.bn + ".running_mean"]),
-                                     ptr(Bf[cv.bn + ".running_var"]), C.c_float(eps[cv.bn]), ptr(cv.wfd), s)
         self.weight_bytes += sum(cv.wfd.numel() * cv.wfd.element_size() for cv in self.convs.values())
 
-    # ------------------------------------------------------------------ forward (keeps the activations)
-    def _forward(self, x: torch.Tensor, probe=None) -> torch.Tensor:
-        """InferenceSession._forward's launches, every activation the backward reads written to its own tensor."""
-        L, dt, s, N = self.L, self.dt, stream(), self.N
-        H, W = self.hw
-        if x.dtype == torch.uint8:
-            L.images_u8_to_nhwc4(dt, N, H, W, ptr(x), ptr(self.x0), s)
-        else:
-            L.images_to_nhwc4(dt, N, H, W, ptr(x), ptr(self.x0), s)
-        H1, W1 = self.stem_hw
-        L.conv_fwd(C.byref(self.stem_desc), dt, ptr(self.x0), ptr(self.stem_wf), ptr(self.y0), None, None, None, s)
-        if probe is not None:
-            probe(self.y0, self.y0.numel())
-        L.maxpool_fwd(dt, N, H1, W1, 64, ptr(self.y0), ptr(self.stem_coef[0]), ptr(self.stem_coef[1]), ptr(self.p0),
-                      ptr(self.amax), s)
-        if probe is not None:
-            probe(self.p0, self.p0.numel())
-        h, yd = self.p0, self.pool[3]
-        for (c1, c2, c3, ds), (a1, a2, out) in zip(self.schedule, self.acts):
-            self._conv(c1, h, a1, None, 1, s, probe)
-            self._conv(c2, a1, a2, None, 1, s, probe)
-            res = h
-            if ds is not None:
-                self._conv(ds, h, yd, None, 0, s, probe)
-                res = yd
-            self._conv(c3, a2, out, res, 1, s, probe)
-            h = out
-        return self._head(h)
+    def _fold(self, cv, master, s) -> None:
+        super()._fold(cv, master, s)
+        self.L.conv_fold_bn_dgrad(C.byref(cv.desc), self.dt, *master, ptr(cv.wfd), s)
+
+    def _buffers(self):
+        """Every activation the backward reads goes to its own tensor (yd, which it does not read, borrows one)."""
+        return self.y0, self.p0, [(*acts, self.pool[3]) for acts in self.acts]
 
     # ------------------------------------------------------------------ backward
     def _keep(self, role: str, t: torch.Tensor, shape=None) -> None:
@@ -203,35 +170,6 @@ class GradientSession(InferenceSession):
         return self.dx
 
     # ------------------------------------------------------------------ public
-    def _check_images(self, images, who: str) -> None:
-        want = (self.batch, 3 * self.n_cams, *self.hw)
-        if not isinstance(images, torch.Tensor) or tuple(images.shape) != want:
-            raise ValueError(f"GradientSession.{who} expects images of shape {want}, got "
-                             f"{tuple(images.shape) if isinstance(images, torch.Tensor) else type(images).__name__}")
-        if images.dtype not in self.static_in:
-            raise ValueError(f"GradientSession.{who} expects float32 or uint8 images, got {images.dtype}")
-
-    def _run(self, kind: str, images: torch.Tensor, body) -> None:
-        """``body(x)`` eagerly on ``images``, or captured once per (kind, input dtype) and replayed."""
-        with torch.cuda.device(self.device), torch.no_grad():
-            if not self.graph:
-                body(images.to(self.device).contiguous())
-                return
-            x = self.static_in[images.dtype]
-            x.copy_(images)
-            g = self._graphs.get((kind, images.dtype))
-            if g is None:
-                side = torch.cuda.Stream(self.device)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):  # untimed warm-up outside the capture
-                    body(x)
-                torch.cuda.current_stream().wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    body(x)
-                self._graphs[kind, images.dtype] = g
-            g.replay()
-
     def vjp(self, images: torch.Tensor, dpred: torch.Tensor) -> torch.Tensor:
         """d<session(images), dpred>/d images: fp32 (batch, 3*n_cams, H, W), a fresh tensor. ``images`` as
         ``session(images)`` takes them (uint8: the gradient with respect to the /255 image); ``dpred`` a
