@@ -14,6 +14,12 @@ reference's own distance from fp64 in brackets):
   64x64:  fp32 e = 4.0e-6, bf16 e = 0.375, d_ref = 0.412 [3.4e-6];  72x104: fp32 e = 4.5e-3, bf16 e = 0.420,
   d_ref = 0.451 [1.4e-4]. Worst stage rel_max / bar: fp32 0.036 (layer4.0.downsample, 72x104), bf16 0.346
   (layer1.2.conv3, 64x64); stem stage 0.018 / 0.072. Worst kernel error / bound: fp32 0.113, bf16 0.191.
+  128x128 (the smallest session with 64-row tiles): fp32 e = 6.2e-3, bf16 e = 0.385, d_ref = 0.430 [9.1e-4]; worst
+  stage rel_max / bar fp32 0.054 (layer3.0.downsample), bf16 0.353 (layer2.1.conv1); forward conv by conv, worst
+  error / bound fp32 0.039, bf16 0.245.
+
+The parity shapes live in tests/infer_shapes.py with the Python mirror of the library's tile-height rule; every
+parity case asserts through the kernel timer that it launched the instantiation the mirror names.
 """
 import ctypes as C
 
@@ -22,6 +28,8 @@ import torch
 import torch.nn as nn
 
 from argus_amd._lib import BF16, F32, ConvDesc, lib, ptr, stream
+from argus_amd.profiling import KernelTimer
+from infer_shapes import DGRAD_PARITY, conv_kernel_name, is_frozen_conv, session_convs
 
 pytestmark = pytest.mark.gpu
 
@@ -82,14 +90,13 @@ def test_fold_dgrad_is_the_forward_fold_permuted_and_flipped(cuda, dt, cin, cout
 
 
 # ---- 2. kernel parity ---------------------------------------------------------------------------------------
-# the shapes of tests/test_gpu_infer.py: (n, h, w, cin, cout, k, stride)
-PARITY = [
-    (1, 6, 10, 64, 64, 1, 1),    # M = 60: below one tile
-    (3, 5, 7, 192, 64, 3, 1),    # ragged M, borders on every side, channels not a power of two
-    (2, 7, 9, 128, 192, 3, 2),   # odd frame, output 4 x 5: the stride predicate with padding
-    (2, 9, 7, 256, 128, 1, 2),   # the downsample kind: three quarters of dx has no tap
-    (2, 8, 8, 512, 512, 3, 1),   # the layer-4 shape that motivates the split
-]
+PARITY = DGRAD_PARITY  # tests/infer_shapes.py: (n, h, w, cin, cout, k, stride)
+
+
+def _only_conv(timer, want, launches):
+    """The one frozen conv instantiation the launches under ``timer`` ran is ``want``, ``launches`` times."""
+    got = {n: v["launches"] for n, v in timer.summary().items() if is_frozen_conv(n)}
+    assert got == {want: launches}, f"launched {got}, expected {launches} of {want}"
 
 
 def _operands(cuda, dt, n, h, w, cin, cout, k, s, seed=0):
@@ -123,25 +130,30 @@ def test_conv_infer_dgrad_parity(cuda, dt, shape):
         assert (~reached).float().mean() > 0.5  # a 1x1 stride-2 conv never reads most of its input
     add64, m64 = addend.double().cpu(), (mask.double().cpu() > 0).double()
     worst = 0.0
-    for use_mask in (False, True):
-        for use_add in (False, True):
-            ref = ct + add64 if use_add else ct
-            ref = ref * m64 if use_mask else ref
-            bound = TOL[dt] * ref.abs().max().item()
-            # where no tap reaches, dx is the (masked) addend, or zero, exactly
-            exact = (add64 if use_add else torch.zeros_like(ct)) * (m64 if use_mask else 1.0)
-            for sp in splits:
-                dx = torch.full(ref.shape, float("nan"), dtype=TDT[dt], device=cuda)
-                L.conv_infer_dgrad(C.byref(d), DT[dt], ptr(dy), ptr(wfd), ptr(addend) if use_add else None,
-                                   ptr(mask) if use_mask else None, ptr(dx), sp, ptr(ws), ws.numel(), stream())
-                got = dx.double().cpu()
-                assert not torch.isnan(got).any(), f"{shape} {dt} splits={sp}: an element of dx was not written"
-                err = (got - ref).abs().max().item()
-                worst = max(worst, err / bound)
-                assert err <= bound, f"{shape} {dt} mask={use_mask} addend={use_add} splits={sp}: {err:.3e} > {bound:.3e}"
-                if shape[6] == 2:
-                    assert torch.equal(got[~reached], exact[~reached]), f"{shape} {dt} splits={sp}: untouched pixels"
-    print(f"conv_infer_dgrad {shape} {dt}: worst error / bound = {worst:.3f} (default splits {default}, max {mx})")
+    with KernelTimer() as timer:
+        for use_mask in (False, True):
+            for use_add in (False, True):
+                ref = ct + add64 if use_add else ct
+                ref = ref * m64 if use_mask else ref
+                bound = TOL[dt] * ref.abs().max().item()
+                # where no tap reaches, dx is the (masked) addend, or zero, exactly
+                exact = (add64 if use_add else torch.zeros_like(ct)) * (m64 if use_mask else 1.0)
+                for sp in splits:
+                    dx = torch.full(ref.shape, float("nan"), dtype=TDT[dt], device=cuda)
+                    L.conv_infer_dgrad(C.byref(d), DT[dt], ptr(dy), ptr(wfd), ptr(addend) if use_add else None,
+                                       ptr(mask) if use_mask else None, ptr(dx), sp, ptr(ws), ws.numel(), stream())
+                    got = dx.double().cpu()
+                    assert not torch.isnan(got).any(), f"{shape} {dt} splits={sp}: an element of dx was not written"
+                    err = (got - ref).abs().max().item()
+                    worst = max(worst, err / bound)
+                    assert err <= bound, \
+                        f"{shape} {dt} mask={use_mask} addend={use_add} splits={sp}: {err:.3e} > {bound:.3e}"
+                    if shape[6] == 2:
+                        assert torch.equal(got[~reached], exact[~reached]), f"{shape} {dt} splits={sp}: untouched pixels"
+    want = conv_kernel_name("dgrad", dt, shape)
+    _only_conv(timer, want, 4 * len(splits))  # the instantiation the tile-height rule names, and no other
+    print(f"conv_infer_dgrad {shape} {dt}: worst error / bound = {worst:.3f} (default splits {default}, max {mx}); "
+          f"{want}")
 
 
 # ---- 3. split determinism and workspace hygiene ------------------------------------------------------------
@@ -170,6 +182,42 @@ def test_split_is_deterministic_and_leaves_tickets_zero(cuda, dt):
     L.conv_infer_dgrad(C.byref(d), DT[dt], ptr(dy), ptr(wfd), ptr(addend), ptr(mask), ptr(dx1), 1, None, 0, stream())
     ref = (ct + addend.double().cpu()) * (mask.double().cpu() > 0)
     assert (dx1.double().cpu() - ref).abs().max().item() <= TOL[dt] * ref.abs().max().item()
+
+
+# test_gpu_infer.py's TICKETS_1056 with cin and cout swapped: dx is 2070 rows x 2048 columns, 33 x 32 = 1056 tiles
+# of 64 rows, past the 1024 tickets of the fixed 4 KB region
+TICKETS_1056 = (1, 45, 46, 2048, 256, 1, 1)
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+def test_forced_split_above_1024_tiles_grows_the_ticket_region(cuda, dt):
+    """The default rule never splits such a grid; a caller may. The ticket region is then 8 KB, the slabs start
+    behind it, and the hand-off works as below 1024 tiles: right, deterministic, every ticket left zero."""
+    L = lib()
+    d, dy, wfd, addend, mask, ct, _ = _operands(cuda, dt, *TICKETS_1056)
+    assert _plan(d, dt)[0] == 1
+    wsb = [_plan(d, dt, s)[2] for s in (2, 3, 4)]
+    slab = wsb[1] - wsb[0]
+    tickets = wsb[0] - 2 * slab  # bytes of ticket words at the start of the workspace
+    assert tickets == 8192 and slab == 1056 * 64 * 64 * 4 and wsb[2] == tickets + 4 * slab
+    ws = torch.zeros(wsb[0], dtype=torch.uint8, device=cuda)  # a workspace of its own, zeroed once only
+    ref = (ct + addend.double().cpu()) * (mask.double().cpu() > 0)
+    bound = TOL[dt] * ref.abs().max().item()
+    outs = []
+    with KernelTimer() as timer:
+        for _ in range(2):
+            dx = torch.full(ct.shape, float("nan"), dtype=TDT[dt], device=cuda)
+            L.conv_infer_dgrad(C.byref(d), DT[dt], ptr(dy), ptr(wfd), ptr(addend), ptr(mask), ptr(dx), 2, ptr(ws),
+                               ws.numel(), stream())
+            outs.append(dx)
+            assert int(ws[:tickets].count_nonzero()) == 0  # every call leaves every ticket byte zero
+    _only_conv(timer, conv_kernel_name("dgrad", dt, TICKETS_1056), 2)
+    assert conv_kernel_name("dgrad", dt, TICKETS_1056).endswith(", 64>")
+    err = (outs[0].double().cpu() - ref).abs().max().item()
+    print(f"conv_infer_dgrad {TICKETS_1056} {dt} splits=2, 1056 tiles: error / bound = {err / bound:.3f}")
+    assert err <= bound, f"{err:.3e} > {bound:.3e}"
+    assert torch.equal(outs[0].view(BITS[dt]), outs[1].view(BITS[dt]))
+    assert int(ws[tickets:].count_nonzero()) > 0  # the slabs were really used
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
@@ -321,8 +369,23 @@ def _stage_references(s, dpred):
     yield "bwd.dx", "stem", ref.view(B, 3 * s.n_cams, H, W)
 
 
+def _planned_kernels(dt, hw, directions, batch=2):
+    """The frozen conv instantiations a session of this size launches, by the mirror of the tile-height rule."""
+    return {conv_kernel_name(direction, dt, shape) for shape in session_convs(batch, hw).values()
+            for direction in directions}
+
+
+def _launched_kernels(timer):
+    return {n for n in timer.summary() if is_frozen_conv(n)}
+
+
+# 72x104: ragged 9x13, 5x7, 3x4; 128x128: the smallest session with 64-row tiles (forward 1x1 s1; backward 1x1 s1, s2)
+SESSION_HW = [(64, 64), (72, 104), (128, 128)]
+SESSION_IDS = ["64x64", "72x104", "128x128"]
+
+
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
-@pytest.mark.parametrize("hw", [(64, 64), (72, 104)], ids=["64x64", "72x104"])  # 72x104: ragged 9x13, 5x7, 3x4
+@pytest.mark.parametrize("hw", SESSION_HW, ids=SESSION_IDS)
 def test_session_stage_by_stage(cuda, oracle, dt, hw):
     from argus_amd.infer_grad import GradientSession
 
@@ -331,7 +394,12 @@ def test_session_stage_by_stage(cuda, oracle, dt, hw):
     x = (_images(hw).float() / 255.0).to(cuda)
     dpred = _cotangent().to(cuda)
     s.dx.fill_(float("nan"))
-    g = s.vjp(x, dpred)
+    with KernelTimer() as timer:
+        g = s.vjp(x, dpred)
+    launched = _launched_kernels(timer)
+    assert launched == _planned_kernels(dt, hw, ("fwd", "dgrad")), launched
+    rows64 = {n for n in launched if n.endswith(", 64>")}
+    assert len(rows64) == (2 if hw == (128, 128) else 0), launched  # forward and data gradient, or neither
     assert g.shape == (2, 6, *hw) and g.dtype == torch.float32 and not torch.isnan(g).any()
     assert len(s.debug) == s.launches_per_backward == 4 + 1 + 52 + 2
     worst, seen = {"stage": (0.0, ""), "stem": (0.0, "")}, 0
@@ -348,6 +416,72 @@ def test_session_stage_by_stage(cuda, oracle, dt, hw):
     assert seen == len(s.debug)
     print(f"frozen gradient stages {dt} {hw}: worst rel_max / bar = {worst['stage'][0]:.3f} at {worst['stage'][1]}, "
           f"stem {worst['stem'][0]:.3f}")
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+@pytest.mark.parametrize("hw", [(72, 104), (128, 128)], ids=["72x104", "128x128"])
+def test_session_forward_conv_by_conv(cuda, oracle, dt, hw):
+    """The forward counterpart of test_session_stage_by_stage: every conv launch of a GradientSession forward against
+    fp64 conv2d of the stored input with the stored folded weight, + bias, + the residual, through the ReLU, at the
+    kernel bars of the parity test (2e-5 / 1.5e-2 of the reference's maximum magnitude). The inputs are the tensors
+    the session keeps for its backward (p0, a1 / a2 / out of every block). The downsample output borrows a pool
+    buffer that the next stride block overwrites, so it is captured here as the backward's _keep captures a
+    gradient: a clone taken right after its launch, checked itself and then used as conv3's residual."""
+    import torch.nn.functional as F
+
+    from argus_amd.infer_grad import GradientSession
+
+    s = GradientSession(_product(oracle, cuda, dt), 2, hw, debug=True)
+    x = (_images(hw).float() / 255.0).to(cuda)
+    yd = {}
+    conv = s._conv
+
+    def conv_and_keep(cv, xin, out, res, relu, st, probe=None):
+        conv(cv, xin, out, res, relu, st, probe)
+        if ".downsample." in cv.name:
+            d = cv.desc
+            yd[cv.name] = out[:d.n * d.ho * d.wo * d.k].view(d.n, d.ho, d.wo, d.k).clone()
+
+    s._conv = conv_and_keep
+    for acts in s.acts:
+        for t in acts:
+            t.fill_(float("nan"))
+    with KernelTimer() as timer:
+        s(x)
+    launched = _launched_kernels(timer)
+    assert launched == _planned_kernels(dt, hw, ("fwd",)), launched
+    assert len({n for n in launched if n.endswith(", 64>")}) == (1 if hw == (128, 128) else 0), launched
+    f64 = lambda t: t.double().cpu()  # noqa: E731
+
+    def ref(cv, xin, res, relu):
+        d = cv.desc
+        w = f64(cv.wf).view(d.k, d.r, d.s, d.c).permute(0, 3, 1, 2)
+        y = F.conv2d(xin.permute(0, 3, 1, 2), w, stride=d.stride, padding=d.pad).permute(0, 2, 3, 1) + f64(cv.bias)
+        y = y if res is None else y + res
+        return y.clamp_min(0) if relu else y
+
+    worst, seen = (0.0, ""), 0
+    h = f64(s.p0)
+    for (c1, c2, c3, ds), (a1, a2, out) in zip(s.schedule, s.acts):
+        a1, a2, out = f64(a1), f64(a2), f64(out)
+        res = h
+        checks = [(c1, a1, ref(c1, h, None, 1)), (c2, a2, ref(c2, a1, None, 1))]
+        if ds is not None:
+            res = f64(yd[ds.name])
+            checks.append((ds, res, ref(ds, h, None, 0)))
+        checks.append((c3, out, ref(c3, a2, res, 1)))
+        for cv, got, want in checks:
+            assert got.shape == want.shape, (cv.name, got.shape, want.shape)
+            bound = TOL[dt] * want.abs().max().item()
+            assert bound > 0, cv.name
+            err = (got - want).abs().max().item()  # NaN (an unwritten element) fails the bound
+            if err / bound > worst[0]:
+                worst = (err / bound, cv.name)
+            assert err <= bound, f"{cv.name} {dt} {hw}: {err:.3e} > {bound:.3e}"
+            seen += 1
+        h = out
+    assert seen == len(s.convs) == 52 and len(yd) == 4
+    print(f"frozen forward convs {dt} {hw}: worst error / bound = {worst[0]:.3f} at {worst[1]}")
 
 
 @pytest.fixture(scope="module")
@@ -378,7 +512,7 @@ def oracle_grads(oracle):
     return get
 
 
-@pytest.mark.parametrize("hw", [(64, 64), (72, 104)], ids=["64x64", "72x104"])
+@pytest.mark.parametrize("hw", SESSION_HW, ids=SESSION_IDS)
 def test_session_matches_the_fp64_oracle(cuda, oracle, oracle_grads, hw):
     """A gross-error check (the decisive ones are the kernel parity and the stages): a deep random ReLU net is
     chaotic in its masks, so the bar is the CPU reference's own bf16 distance, doubled as in

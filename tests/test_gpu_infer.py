@@ -6,6 +6,11 @@ argus_bn_eval_coeffs. The session is held to the fp64 oracle in eval mode with n
 fp32 within 1e-4 absolute (the project's fp32 bar; the CPU fp32 oracle itself is 7e-6 from fp64 with this
 recipe at |pred| <= 13), bf16 within 2x the distance of the existing compute_dtype="bf16" model.eval() forward
 measured in the same test.
+
+The parity shapes live in tests/infer_shapes.py with the Python mirror of the library's tile-height rule
+(64-row tiles from cdiv(M, 64) * (N / 64) >= 256). Every parity case asserts, through the kernel timer, that it
+launched the instantiation the mirror names; test_deployed_kernel_selection_is_covered_by_the_parity_shapes
+requires every instantiation a 256 x 256 session launches to be among those the parity shapes launch.
 """
 import ctypes as C
 
@@ -14,7 +19,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from argus_amd._lib import BF16, F32, ConvDesc, lib, ptr, stream
+from argus_amd._lib import BF16, F16, F32, ConvDesc, lib, ptr, stream
+from argus_amd.profiling import KernelTimer
+from infer_shapes import DGRAD_PARITY, FWD_PARITY, conv_kernel_name, is_frozen_conv
 
 pytestmark = pytest.mark.gpu
 
@@ -60,14 +67,13 @@ def test_fold_is_bit_exact(cuda, dt, cin, cout, k):
 
 
 # ---- 2. kernel parity ---------------------------------------------------------------------------------------
-# the smallest shapes that reach each failure mode: (n, h, w, cin, cout, k, stride)
-PARITY = [
-    (1, 6, 10, 64, 64, 1, 1),    # M = 60: below one tile
-    (3, 5, 7, 192, 64, 3, 1),    # ragged M, borders on every side, channels not a power of two
-    (2, 7, 9, 128, 192, 3, 2),   # odd frame, output 4 x 5
-    (2, 9, 7, 256, 128, 1, 2),   # the downsample kind
-    (2, 8, 8, 512, 512, 3, 1),   # the layer-4 shape that motivates the split
-]
+PARITY = FWD_PARITY  # tests/infer_shapes.py (test_gpu_infer_f16.py runs the same table)
+
+
+def _only_conv(timer, want, launches):
+    """The one frozen conv instantiation the launches under ``timer`` ran is ``want``, ``launches`` times."""
+    got = {n: v["launches"] for n, v in timer.summary().items() if is_frozen_conv(n)}
+    assert got == {want: launches}, f"launched {got}, expected {launches} of {want}"
 
 
 def _operands(cuda, dt, n, h, w, cin, cout, k, s, seed=0):
@@ -96,19 +102,22 @@ def test_conv_infer_parity(cuda, dt, shape):
     ws = torch.zeros(nbytes, dtype=torch.uint8, device=cuda)  # zeroed once for all the calls below
     splits = sorted({min(s, mx) for s in (1, 2, 3, mx)}) + [0]  # 3 / the maximum: uneven / single-k-step slices
     worst = 0.0
-    for use_res in (False, True):
-        for relu in (0, 1):
-            ref = y + resd if use_res else y
-            ref = ref.clamp_min(0) if relu else ref
-            bound = TOL[dt] * ref.abs().max().item()
-            for sp in splits:
-                out = torch.full(ref.shape, float("nan"), dtype=TDT[dt], device=cuda)
-                L.conv_infer(C.byref(d), DT[dt], ptr(x), ptr(wf), ptr(bias), ptr(res) if use_res else None, relu,
-                             ptr(out), sp, ptr(ws), ws.numel(), stream())
-                err = (out.double().cpu() - ref).abs().max().item()
-                worst = max(worst, err / bound)
-                assert err <= bound, f"{shape} {dt} res={use_res} relu={relu} splits={sp}: {err:.3e} > {bound:.3e}"
-    print(f"conv_infer {shape} {dt}: worst error / bound = {worst:.3f} (default splits {default}, max {mx})")
+    with KernelTimer() as timer:
+        for use_res in (False, True):
+            for relu in (0, 1):
+                ref = y + resd if use_res else y
+                ref = ref.clamp_min(0) if relu else ref
+                bound = TOL[dt] * ref.abs().max().item()
+                for sp in splits:
+                    out = torch.full(ref.shape, float("nan"), dtype=TDT[dt], device=cuda)
+                    L.conv_infer(C.byref(d), DT[dt], ptr(x), ptr(wf), ptr(bias), ptr(res) if use_res else None, relu,
+                                 ptr(out), sp, ptr(ws), ws.numel(), stream())
+                    err = (out.double().cpu() - ref).abs().max().item()
+                    worst = max(worst, err / bound)
+                    assert err <= bound, f"{shape} {dt} res={use_res} relu={relu} splits={sp}: {err:.3e} > {bound:.3e}"
+    want = conv_kernel_name("fwd", dt, shape)
+    _only_conv(timer, want, 4 * len(splits))  # the instantiation the tile-height rule names, and no other
+    print(f"conv_infer {shape} {dt}: worst error / bound = {worst:.3f} (default splits {default}, max {mx}); {want}")
 
 
 # ---- 3. split determinism and workspace hygiene ------------------------------------------------------------
@@ -135,6 +144,41 @@ def test_split_is_deterministic_and_leaves_tickets_zero(cuda, dt):
     L.conv_infer(C.byref(d), DT[dt], ptr(x), ptr(wf), ptr(bias), ptr(res), 1, ptr(out1), 1, None, 0, stream())
     ref = (y + resd).clamp_min(0)
     assert (out1.double().cpu() - ref).abs().max().item() <= TOL[dt] * ref.abs().max().item()
+
+
+# M = 2070 rows x 2048 columns: 33 x 32 = 1056 tiles of 64 rows, past the 1024 tickets of the fixed 4 KB region
+TICKETS_1056 = (1, 45, 46, 256, 2048, 1, 1)
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+def test_forced_split_above_1024_tiles_grows_the_ticket_region(cuda, dt):
+    """The default rule never splits such a grid; a caller may. The ticket region is then 8 KB, the slabs start
+    behind it, and the hand-off works as below 1024 tiles: right, deterministic, every ticket left zero."""
+    L = lib()
+    d, x, wf, bias, res, y, resd = _operands(cuda, dt, *TICKETS_1056)
+    assert L.dll.argus_conv_infer_splits(C.byref(d), DT[dt]) == 1
+    wsb = [L.dll.argus_conv_infer_workspace_bytes(C.byref(d), DT[dt], s) for s in (2, 3, 4)]
+    slab = wsb[1] - wsb[0]
+    tickets = wsb[0] - 2 * slab  # bytes of ticket words at the start of the workspace
+    assert tickets == 8192 and slab == 1056 * 64 * 64 * 4 and wsb[2] == tickets + 4 * slab
+    ws = torch.zeros(wsb[0], dtype=torch.uint8, device=cuda)  # a workspace of its own, zeroed once only
+    ref = (y + resd).clamp_min(0)
+    bound = TOL[dt] * ref.abs().max().item()
+    outs = []
+    with KernelTimer() as timer:
+        for _ in range(2):
+            out = torch.full(y.shape, float("nan"), dtype=TDT[dt], device=cuda)
+            L.conv_infer(C.byref(d), DT[dt], ptr(x), ptr(wf), ptr(bias), ptr(res), 1, ptr(out), 2, ptr(ws),
+                         ws.numel(), stream())
+            outs.append(out)
+            assert int(ws[:tickets].count_nonzero()) == 0  # every call leaves every ticket byte zero
+    _only_conv(timer, conv_kernel_name("fwd", dt, TICKETS_1056), 2)
+    assert conv_kernel_name("fwd", dt, TICKETS_1056).endswith(", 64>")
+    err = (outs[0].double().cpu() - ref).abs().max().item()
+    print(f"conv_infer {TICKETS_1056} {dt} splits=2, 1056 tiles: error / bound = {err / bound:.3f}")
+    assert err <= bound, f"{err:.3e} > {bound:.3e}"
+    assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
+    assert int(ws[tickets:].count_nonzero()) > 0  # the slabs were really used
 
 
 # ---- 4 / 5. the session ------------------------------------------------------------------------------------
@@ -178,29 +222,115 @@ def oracle_fp64(oracle):
     import copy
 
     ref64 = copy.deepcopy(oracle).double().eval()
-    out = {}
-    with torch.no_grad():
-        for hw in ((64, 64), (72, 104)):
-            out[hw] = ref64((_images(hw).float() / 255.0).double())
-    return out
+
+    class PerSize(dict):  # each size on first use
+        def __missing__(self, hw):
+            with torch.no_grad():
+                self[hw] = ref64((_images(hw).float() / 255.0).double())
+            return self[hw]
+
+    return PerSize()
 
 
-@pytest.mark.parametrize("hw", [(64, 64), (72, 104)], ids=["64x64", "72x104"])  # 72x104: ragged 9x13, 5x7, 3x4
+# 72x104: ragged 9x13, 5x7, 3x4; 128x128: the smallest session that runs 64-row tiles (1x1 s1 convs of layer1)
+SESSION_HW = [(64, 64), (72, 104), (128, 128)]
+SESSION_IDS = ["64x64", "72x104", "128x128"]
+
+
+@pytest.mark.parametrize("hw", SESSION_HW, ids=SESSION_IDS)
 def test_session_matches_the_fp64_oracle(cuda, oracle, oracle_fp64, hw):
+    """The fp32 bar of 1e-4 is absolute and was set at 64x64 / 72x104, where the CPU fp32 oracle is itself 7e-6
+    from fp64. At 128x128 the bar is the larger of 1e-4 and 8 x the CPU fp32 oracle's own distance from the fp64
+    oracle, measured here on the reference alone (8: about the margin 1e-4 has over 7e-6, halved). Measured: that
+    distance is 9.2e-6 at 128x128 (|pred| <= 24.9; 1.5e-5 with another CPU's thread count), so the bar there is
+    still 1e-4; the fp32 session is 1.1e-5 from fp64 at 128x128, 4.9e-6 at 64x64, 1.3e-5 at 72x104."""
     from argus_amd.infer import InferenceSession
 
-    x = (_images(hw).float() / 255.0).to(cuda)
+    xc = _images(hw).float() / 255.0
+    x = xc.to(cuda)
     ref = oracle_fp64[hw]
+    with torch.no_grad():
+        d_cpu32 = (oracle(xc).double() - ref).abs().max().item()  # the reference only
+    bar32 = max(1e-4, 8 * d_cpu32) if hw == (128, 128) else 1e-4
     m32 = _product(oracle, cuda, "fp32")
     d32 = (InferenceSession(m32, 2, hw)(x).double().cpu() - ref).abs().max().item()
     m16 = _product(oracle, cuda, "bf16")
     with torch.no_grad():
         d_eval = (m16(x).double().cpu() - ref).abs().max().item()  # the existing bf16 eval path
     d16 = (InferenceSession(m16, 2, hw)(x).double().cpu() - ref).abs().max().item()
-    print(f"session vs fp64 oracle {hw}: fp32 {d32:.3e}; bf16 session {d16:.3e}, bf16 model.eval() {d_eval:.3e}; "
-          f"max |pred| {ref.abs().max().item():.2f}")
-    assert d32 <= 1e-4
+    print(f"session vs fp64 oracle {hw}: fp32 {d32:.3e} (bar {bar32:.3e}; CPU fp32 oracle {d_cpu32:.3e}); "
+          f"bf16 session {d16:.3e}, bf16 model.eval() {d_eval:.3e}; max |pred| {ref.abs().max().item():.2f}")
+    assert d32 <= bar32
     assert d16 <= 2 * d_eval
+
+
+def _frozen_kernels(fn):
+    """Names of the frozen conv instantiations ``fn`` launches (the library's kernel timer)."""
+    with KernelTimer() as kt:
+        fn()
+    return {n for n in kt.summary() if is_frozen_conv(n)}
+
+
+def test_deployed_kernel_selection_is_covered_by_the_parity_shapes(cuda, oracle):
+    """The pattern of test_gpu_parity.py::test_benched_kernel_selection_block_backward_stages for the frozen path:
+    eager sessions at the deployed 256 x 256, B = 1 and B = 2 (InferenceSession in fp32 / bf16 / fp16,
+    GradientSession.vjp in fp32 / bf16) record the frozen conv instantiations they launch; every one of them must
+    also be launched by a shape of the parity tables (FWD_PARITY in the three dtypes, DGRAD_PARITY in two), which
+    are what compares these kernels with fp64. Only launches here, no oracle."""
+    from argus_amd.infer import InferenceSession
+    from argus_amd.infer_grad import GradientSession
+
+    L = lib()
+    model = _product(oracle, cuda, "fp32")
+    hw = (256, 256)
+    want = {}
+    for batch in (1, 2):
+        x = _images(hw, batch=batch).to(cuda)
+        cot = torch.ones(batch, 6, device=cuda)
+        for dt in ("fp32", "bf16", "fp16"):
+            s = InferenceSession(model, batch, hw, compute_dtype=dt, graph=False)
+            for n in _frozen_kernels(lambda: s(x)):
+                want.setdefault(n, f"InferenceSession {dt} B = {batch}")
+        for dt in ("fp32", "bf16"):
+            g = GradientSession(model, batch, hw, compute_dtype=dt, graph=False)
+            for n in _frozen_kernels(lambda: g.vjp(x, cot)):
+                want.setdefault(n, f"GradientSession.vjp {dt} B = {batch}")
+        del s, g
+    # a default split keeps tiles * splits <= 256: at most 4 KB of tickets + 256 slabs of 16 KB
+    ws = torch.zeros(1 << 23, dtype=torch.uint8, device=cuda)
+    tdt, code = {**TDT, "fp16": torch.float16}, {**DT, "fp16": F16}
+
+    def parity_launches():
+        for dt in ("fp32", "bf16", "fp16"):
+            for n, h, w, cin, cout, k, st in FWD_PARITY:
+                d = _desc(n, h, w, cin, cout, k, st)
+                xin = torch.zeros(n, h, w, cin, dtype=tdt[dt], device=cuda)
+                wf = torch.zeros(cout, k * k * cin, dtype=tdt[dt], device=cuda)
+                bias = torch.zeros(cout, device=cuda)
+                out = torch.empty(n, d.ho, d.wo, cout, dtype=tdt[dt], device=cuda)
+                L.conv_infer(C.byref(d), code[dt], ptr(xin), ptr(wf), ptr(bias), None, 1, ptr(out), 0, ptr(ws),
+                             ws.numel(), stream())
+            if dt == "fp16":
+                continue
+            for n, h, w, cin, cout, k, st in DGRAD_PARITY:
+                d = _desc(n, h, w, cin, cout, k, st)
+                dy = torch.zeros(n, d.ho, d.wo, cout, dtype=tdt[dt], device=cuda)
+                wfd = torch.zeros(cin, k * k * cout, dtype=tdt[dt], device=cuda)
+                dx = torch.empty(n, h, w, cin, dtype=tdt[dt], device=cuda)
+                L.conv_infer_dgrad(C.byref(d), code[dt], ptr(dy), ptr(wfd), None, None, ptr(dx), 0, ptr(ws), ws.numel(),
+                                   stream())
+        torch.cuda.synchronize()
+
+    have = _frozen_kernels(parity_launches)
+    assert int(ws[:4096].count_nonzero()) == 0
+    missing = sorted(set(want) - have)
+    assert not missing, "frozen conv kernels of a deployed session that no parity shape launches: " + "; ".join(
+        f"{n} ({want[n]})" for n in missing)
+    assert {n for n in want if n.endswith(", 64>")} == {
+        f"argus::{fam}<{t}, 64>" for fam, ts in (("conv_infer_kernel", ("float", "__bf16", "_Float16")),
+                                                   ("conv_infer_dgrad_kernel", ("float", "__bf16"))) for t in ts}
+    print(f"deployed 256 x 256 sessions launch {len(want)} frozen conv instantiations, the parity shapes {len(have)}: "
+          f"{sorted(want)}")
 
 
 class _Count:

@@ -15,6 +15,8 @@ import torch.nn.functional as F
 
 import test_gpu_infer as base
 from argus_amd._lib import BF16, F16, ConvDesc, lib, ptr, stream
+from argus_amd.profiling import KernelTimer
+from infer_shapes import conv_kernel_name
 from test_gpu_infer import PARITY, _bn_params, _desc, _images, _operands, _product, oracle, oracle_fp64  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -78,19 +80,22 @@ def test_conv_infer_parity_fp16(cuda, shape):
     ws = torch.zeros(nbytes, dtype=torch.uint8, device=cuda)  # zeroed once for all the calls below
     splits = sorted({min(s, mx) for s in (1, 2, 3, mx)}) + [0]
     worst = 0.0
-    for use_res in (False, True):
-        for relu in (0, 1):
-            ref = y + resd if use_res else y
-            ref = ref.clamp_min(0) if relu else ref
-            bound = TOL16 * ref.abs().max().item()
-            for sp in splits:
-                out = torch.full(ref.shape, float("nan"), dtype=torch.float16, device=cuda)
-                L.conv_infer(C.byref(d), F16, ptr(x), ptr(wf), ptr(bias), ptr(res) if use_res else None, relu,
-                             ptr(out), sp, ptr(ws), ws.numel(), stream())
-                err = (out.double().cpu() - ref).abs().max().item()  # NaN (an unwritten element) fails the bound
-                worst = max(worst, err / bound)
-                assert err <= bound, f"{shape} fp16 res={use_res} relu={relu} splits={sp}: {err:.3e} > {bound:.3e}"
-    print(f"conv_infer {shape} fp16: worst error / bound = {worst:.3f} (default splits {default}, max {mx})")
+    with KernelTimer() as timer:
+        for use_res in (False, True):
+            for relu in (0, 1):
+                ref = y + resd if use_res else y
+                ref = ref.clamp_min(0) if relu else ref
+                bound = TOL16 * ref.abs().max().item()
+                for sp in splits:
+                    out = torch.full(ref.shape, float("nan"), dtype=torch.float16, device=cuda)
+                    L.conv_infer(C.byref(d), F16, ptr(x), ptr(wf), ptr(bias), ptr(res) if use_res else None, relu,
+                                 ptr(out), sp, ptr(ws), ws.numel(), stream())
+                    err = (out.double().cpu() - ref).abs().max().item()  # NaN (an unwritten element) fails the bound
+                    worst = max(worst, err / bound)
+                    assert err <= bound, f"{shape} fp16 res={use_res} relu={relu} splits={sp}: {err:.3e} > {bound:.3e}"
+    want = conv_kernel_name("fwd", "fp16", shape)
+    base._only_conv(timer, want, 4 * len(splits))  # the instantiation the tile-height rule names, and no other
+    print(f"conv_infer {shape} fp16: worst error / bound = {worst:.3f} (default splits {default}, max {mx}); {want}")
 
 
 # ---- 6. saturation ------------------------------------------------------------------------------------------
@@ -226,7 +231,8 @@ def test_pools_fp16(cuda):
 
 
 # ---- 10. the session against the fp64 oracle --------------------------------------------------------------------
-@pytest.mark.parametrize("hw", [(64, 64), (72, 104)], ids=["64x64", "72x104"])  # LDS-patch stem / fallback stem
+# LDS-patch stem / fallback stem / the smallest session with 64-row conv tiles (LDS-patch stem)
+@pytest.mark.parametrize("hw", base.SESSION_HW, ids=base.SESSION_IDS)
 def test_fp16_session_matches_the_fp64_oracle(cuda, oracle, oracle_fp64, hw):
     """d = max |prediction - fp64 oracle|, B = 2. Measured on an MI355X: 64x64 fp16 session
     9.58e-3, reference fp16 autocast 7.74e-3, bf16 session 3.77e-2; 72x104 7.44e-3, 1.20e-2, 4.45e-2."""

@@ -51,6 +51,61 @@ def test_split_planning():
     assert ws[2] - 2 * (ws[3] - ws[2]) > 0  # the ticket words
 
 
+DEPLOYED = [(1, (256, 256)), (2, (256, 256)), (1, (376, 672))]  # the sizes behind the README's latency figures
+
+
+def test_every_kernel_class_of_a_deployed_session_is_in_the_parity_tables():
+    """Every conv of a session plan at the deployed sizes, forward and data gradient, fp32 and 16-bit, classified
+    as (direction, dtype group, kernel size, stride, tile rows by the Python mirror of infer_bm(), default splits
+    > 1 from the library's own planning): each class must also occur among the kernel-parity shapes of the GPU
+    tests, classified the same way. (The GPU tests hold the mirror to the kernel names the library launches.)"""
+    import infer_shapes as S
+    from argus_amd._lib import BF16, F16, F32, lib
+
+    L = lib()
+    code = {"fp32": F32, "bf16": BF16, "fp16": F16}
+    served = {"fwd": ("fp32", "bf16", "fp16"), "dgrad": ("fp32", "bf16")}
+    tables = {"fwd": S.FWD_PARITY, "dgrad": S.DGRAD_PARITY}
+    have = {S.conv_class(L, direction, dt, code[dt], shape)
+            for direction in tables for dt in served[direction] for shape in tables[direction]}
+    missing, need = {}, set()
+    for batch, hw in DEPLOYED:
+        for name, shape in S.session_convs(batch, hw).items():
+            for direction in tables:
+                for dt in served[direction]:
+                    cls = S.conv_class(L, direction, dt, code[dt], shape)
+                    need.add(cls)
+                    if cls not in have:
+                        missing.setdefault(cls, f"{name} {shape} at {hw[0]}x{hw[1]}, B = {batch}, {dt}")
+    assert len(S.session_convs(1, (256, 256))) == 52
+    # what this guards: the deployed sizes do run 64-row tiles, of every kind, in both directions
+    assert {c[:5] for c in need if c[4] == 64} == {
+        (direction, grp, k, s, 64) for direction in tables for grp in ("fp32", "16-bit")
+        for k, s in ((1, 1), (1, 2), (3, 1), (3, 2)) if (direction, k, s) != ("fwd", 3, 2)}
+    assert not missing, "kernel classes of a deployed session that no parity shape runs:\n" + "\n".join(
+        f"  {c}: e.g. {missing[c]}" for c in sorted(missing))
+
+
+def test_the_tile_height_mirror_on_the_documented_thresholds():
+    """infer_shapes.infer_bm at the two deployed shapes that sit exactly on the rule's threshold, their neighbours
+    below, and a whole session: 128 x 128 at B = 2 is the smallest tested session that selects 64-row tiles."""
+    import infer_shapes as S
+
+    assert S.infer_bm(*S.gemm_mn("fwd", 2, 32, 32, 128, 512, 1, 1)) == 64   # 32 * 8 = 256
+    assert S.infer_bm(*S.gemm_mn("fwd", 2, 32, 31, 128, 512, 1, 1)) == 32   # 31 * 8 = 248
+    assert S.infer_bm(*S.gemm_mn("dgrad", 2, 64, 64, 128, 128, 3, 2)) == 64  # 128 * 2 = 256
+    assert S.infer_bm(*S.gemm_mn("dgrad", 2, 64, 63, 128, 128, 3, 2)) == 32  # 126 * 2 = 252
+    assert S.conv_kernel_name("fwd", "fp16", (2, 32, 32, 128, 512, 1, 1)) == "argus::conv_infer_kernel<_Float16, 64>"
+    assert S.conv_kernel_name("dgrad", "bf16", (1, 6, 10, 64, 64, 1, 1)) == "argus::conv_infer_dgrad_kernel<__bf16, 32>"
+
+    def rows(batch, hw):
+        return {(direction, S.infer_bm(*S.gemm_mn(direction, *shape)))
+                for shape in S.session_convs(batch, hw).values() for direction in ("fwd", "dgrad")}
+
+    assert rows(2, (64, 64)) == rows(2, (72, 104)) == {("fwd", 32), ("dgrad", 32)}
+    assert rows(2, (128, 128)) == {("fwd", 32), ("dgrad", 32), ("fwd", 64), ("dgrad", 64)}
+
+
 def test_error_channel():
     from argus_amd._lib import ArgusHipError, ConvDesc, lib
 
