@@ -23,6 +23,7 @@
 #include "internal.h"
 #include "ktimer.h"
 #include "igemm.h"
+#include "lds_dma.h"
 
 namespace argus {
 
@@ -153,28 +154,14 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
   // (checked on the host)
   int a_off[AR], a_ih[AR], a_iw[AR];
   bool a_ok[AR];
+  // 1x1 / stride-1 GEMM (one tap at offset 0, input grid = GEMM row grid): input pixel = GEMM row
   const int HWq = ph.Hq * ph.Wq;
-  // 1x1 / stride-1 GEMM (one tap at offset 0, input grid = GEMM row grid): input pixel = GEMM row, so
-  // no (image, row, column) split is needed (its integer divisions made the small-K 1x1 convs
-  // VALU-bound: SQ_INSTS_VALU 9-20x SQ_INSTS_MFMA)
-  const bool a_ident = !STEM && ph.K == p.Cin && ph.dh[0] == 0 && ph.dw[0] == 0 && p.ish == 1 && p.isw == 1 &&
-                       ph.Hq == p.H && ph.Wq == p.W;
+  const bool a_ident = !STEM && a_rows_ident(p, &ph);
 #pragma unroll
   for (int i = 0; i < AR; ++i) {
     const int m = mt * BM + (tid >> 3) + 32 * i;
     a_ok[i] = m < ph.M;
-    const int mm = a_ok[i] ? m : 0;
-    if (a_ident) {
-      a_ih[i] = 0;
-      a_iw[i] = 0;
-      a_off[i] = mm * p.lda;
-    } else {
-      const int nimg = mm / HWq, rem = mm - nimg * HWq;
-      const int qh = rem / ph.Wq, qw = rem - qh * ph.Wq;
-      a_ih[i] = qh * p.ish;
-      a_iw[i] = qw * p.isw;
-      a_off[i] = ((nimg * p.H + a_ih[i]) * p.W + a_iw[i]) * p.lda;
-    }
+    a_row_offset(p, ph, HWq, a_ok[i] ? m : 0, a_ident, a_off[i], a_ih[i], a_iw[i]);
   }
   const T* b_row[BR];
 #pragma unroll
@@ -499,48 +486,10 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
   // ---- BN statistics of this tile: {sum, M2} per column (fp32 accumulators) ----
   if (p.stats) {
     float2* red = reinterpret_cast<float2*>(lds);  // [2][BN]
-    int nvalid_w = ph.M - (mt * BM + wm * (BM / 2));
-    nvalid_w = nvalid_w < 0 ? 0 : (nvalid_w > BM / 2 ? BM / 2 : nvalid_w);
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      float s = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool ok = mi * 16 + g * 4 + r < nvalid_w;
-          s += ok ? acc[mi][ni][r] : 0.f;
-        }
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const float mean_w = nvalid_w > 0 ? s / (float)nvalid_w : 0.f;
-      float q = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float d = acc[mi][ni][r] - mean_w;
-          q = mi * 16 + g * 4 + r < nvalid_w ? fmaf(d, d, q) : q;
-        }
-      q += __shfl_xor(q, 16, 64);
-      q += __shfl_xor(q, 32, 64);
-      if (lane < 16) red[wm * BN + wn * (BN / 2) + ni * 16 + lane] = make_float2(s, q);
-    }
+    bn_stats_wave<256, BN, 2>(tid, lane, g, acc, StatRowsBelow<BM / 2>(ph.M - mt * BM, wm), false, red, wm, wn * (BN / 2),
+                              p.stats + nt * BN, p.N, (size_t)mt);
     __syncthreads();
-    if (tid < BN) {
-      int na = ph.M - mt * BM;
-      na = na < 0 ? 0 : (na > BM / 2 ? BM / 2 : na);
-      int nb = ph.M - (mt * BM + BM / 2);
-      nb = nb < 0 ? 0 : (nb > BM / 2 ? BM / 2 : nb);
-      const float2 a0 = red[tid], a1 = red[BN + tid];
-      float m2 = a0.y + a1.y;
-      if (na > 0 && nb > 0) {
-        const float d = a0.x / (float)na - a1.x / (float)nb;
-        m2 += d * d * ((float)na * (float)nb / (float)(na + nb));
-      }
-      store_part(p.stats + (size_t)mt * p.N + nt * BN + tid, make_float2(a0.x + a1.x, m2));
-    }
-    __syncthreads();
+    bn_stats_merge<256, BN, 2>(tid, StatRowsBelow<BM / 2>(ph.M - mt * BM, wm), false, red, p.stats + nt * BN, p.N, (size_t)mt);
     if (p.ffin.mode) {  // the statistics finalize folded in (bnfin.h): one partial row per row tile
       bn_fwd_fin_arrive<256, BN>(p.ffin, mt, nt, reinterpret_cast<double2*>(lds), &fin_flag);
       __syncthreads();
@@ -562,7 +511,7 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
   T* Ys = Cs + BM * LD;  // YREC: the recomputed y tile
   T* __restrict__ Cg = reinterpret_cast<T*>(p.c);
   // output pixel = GEMM row (forward, stride-1 dgrad): no division per stored row
-  const bool c_ident = p.osh == 1 && p.osw == 1 && ph.oh0 == 0 && ph.ow0 == 0 && ph.Hq == p.Ho && ph.Wq == p.Wo;
+  const bool c_ident = c_rows_ident(p, ph);
   if constexpr (YREC) {
     // y = conv1x1(yx, yw) of this tile's rows and columns, accumulated exactly as the forward GEMM does
     // (k-steps of 64 in order, two 32-k MFMAs each, operands as the forward's LDS fragments), so the
@@ -575,13 +524,7 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
       const int m = mt * BM + wm * (BM / 2) + mi * 16 + i16;
-      const int mm = m < ph.M ? m : 0;
-      int px = mm;
-      if (!c_ident) {
-        const int nimg = mm / HWq, rem = mm - nimg * HWq;
-        const int qh = rem / ph.Wq, qw = rem - qh * ph.Wq;
-        px = (nimg * p.Ho + qh * p.osh + ph.oh0) * p.Wo + qw * p.osw + ph.ow0;
-      }
+      const int px = gemm_row_offset(p, ph, HWq, m < ph.M ? m : 0, c_ident);
       xo[mi] = px * K2;
     }
     const T* wrow = W2 + (size_t)(nt * BN + wn * (BN / 2) + i16) * K2;
@@ -631,94 +574,98 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgParams p) {
   }
 #pragma unroll
   for (int q = 0; q < EPASS; ++q) {
-    if (EPASS == 1 || wm == q) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = (EPASS == 1 ? wm * (BM / 2) : 0) + mi * 16 + g * 4 + r;
-            const int col = wn * (BN / 2) + ni * 16 + i16;
-            Cs[row * LD + col] = from_f32<T>(acc[mi][ni][r]);
-          }
-    }
+    if (EPASS == 1 || wm == q) epi_stage<T, LD>(g, i16, acc, Cs, EPASS == 1 ? wm * (BM / 2) : 0, wn * (BN / 2));
     __syncthreads();
-    const int c = tid % CPR;
-    constexpr int NIT = ROWS / RPP, U = NIT < 4 ? NIT : 4;
-    static_assert(NIT * RPP == ROWS && NIT % U == 0, "epilogue row partition");
+    const EpiRows rows{p, ph, HWq, mt * BM + q * ROWS, c_ident};
+    if constexpr (OUT) {  // argus_bn_apply's arithmetic on the stored (rounded) y, bit for bit
+      const int c = tid % CPR;
+      constexpr int NIT = ROWS / RPP, U = NIT < 4 ? NIT : 4;
+      static_assert(NIT * RPP == ROWS && NIT % U == 0, "epilogue row partition");
 #pragma unroll
-    for (int i0 = 0; i0 < NIT; i0 += U) {
-      size_t off[U];
-      bool ok[U];
-      EpiIn in[U];
+      for (int i0 = 0; i0 < NIT; i0 += U) {
+        size_t off[U];
+        bool ok[U];
+        u32x4 res[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int rr = tid / CPR + RPP * (i0 + u);
-        const int m = mt * BM + q * ROWS + rr;
-        ok[u] = m < ph.M;
-        const int mm = ok[u] ? m : 0;
-        if (c_ident) {
-          off[u] = (size_t)mm * p.ldc + nt * BN + c * E;
-        } else {
-          const int nimg = mm / HWq, rem = mm - nimg * HWq;
-          const int qh = rem / ph.Wq, qw = rem - qh * ph.Wq;
-          const int oh = qh * p.osh + ph.oh0, ow = qw * p.osw + ph.ow0;
-          off[u] = (((size_t)nimg * p.Ho + oh) * p.Wo + ow) * p.ldc + nt * BN + c * E;
+        for (int u = 0; u < U; ++u) {
+          size_t px;
+          ok[u] = rows(tid / CPR + RPP * (i0 + u), px);
+          off[u] = px * p.ldc + nt * BN + c * E;
+          if (ok[u]) res[u] = ld16(reinterpret_cast<const T*>(p.oe.res) + off[u]);
         }
-        if constexpr (OUT) {
-          if (ok[u]) in[u].add = ld16(reinterpret_cast<const T*>(p.oe.res) + off[u]);
-        } else if constexpr (YREC) {
-          if (ok[u]) {
-            epi_load<T, BW, false>(p, off[u], in[u]);
-            in[u].y = *reinterpret_cast<const u32x4*>(Ys + rr * LD + c * E);
-          }
-        } else if (ok[u]) {
-          epi_load<T, BW>(p, off[u], in[u]);
-        }
-      }
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (!ok[u]) continue;
-        const int rr = tid / CPR + RPP * (i0 + u);
-        const u32x4 v = *reinterpret_cast<const u32x4*>(Cs + rr * LD + c * E);
-        if constexpr (OUT) {  // argus_bn_apply's arithmetic on the stored (rounded) y, bit for bit
+        for (int u = 0; u < U; ++u) {
+          if (!ok[u]) continue;
+          const int rr = tid / CPR + RPP * (i0 + u);
+          const u32x4 v = *reinterpret_cast<const u32x4*>(Cs + rr * LD + c * E);
           if (Cg) st16_nt(Cg + off[u], v);
           float f[E], r[E];
           unpack(v, f);
-          unpack(in[u].add, r);
+          unpack(res[u], r);
 #pragma unroll
           for (int j = 0; j < E; ++j) f[j] = fmaxf(fmaf(f[j], oa[j], ob[j]) + fmaf(r[j], ra[j], rb[j]), 0.f);
           const u32x4 o = pack(f);
           st16(reinterpret_cast<T*>(p.oe.out) + off[u], o);
           p.oe.bits[off[u] / E] = chunk_positive_bits<T>(o);
-        } else {
+        }
+      }
+    } else if constexpr (BM == 64 && BN == 64) {
+      // epi_store's loop written out: through the shared routine the two-stage 64 x 64 apply-prologue forms
+      // (OCC 2, BWX 18 / 19 / 20) need 170 VGPRs instead of 168 and lose their third wave per SIMD
+      const int c = tid % CPR;
+      constexpr int NIT = ROWS / RPP, U = NIT < 4 ? NIT : 4;
+      static_assert(NIT * RPP == ROWS && NIT % U == 0, "epilogue row partition");
+#pragma unroll
+      for (int i0 = 0; i0 < NIT; i0 += U) {
+        size_t off[U];
+        bool ok[U];
+        EpiIn in[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int rr = tid / CPR + RPP * (i0 + u);
+          const int m = mt * BM + q * ROWS + rr;
+          ok[u] = m < ph.M;
+          const int mm = ok[u] ? m : 0;
+          if (c_ident) {
+            off[u] = (size_t)mm * p.ldc + nt * BN + c * E;
+          } else {
+            const int nimg = mm / HWq, rem = mm - nimg * HWq;
+            const int qh = rem / ph.Wq, qw = rem - qh * ph.Wq;
+            const int oh = qh * p.osh + ph.oh0, ow = qw * p.osw + ph.ow0;
+            off[u] = (((size_t)nimg * p.Ho + oh) * p.Wo + ow) * p.ldc + nt * BN + c * E;
+          }
+          if constexpr (YREC) {
+            if (ok[u]) {
+              epi_load<T, BW, false>(p, off[u], in[u]);
+              in[u].y = *reinterpret_cast<const u32x4*>(Ys + rr * LD + c * E);
+            }
+          } else if (ok[u]) {
+            epi_load<T, BW>(p, off[u], in[u]);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (!ok[u]) continue;
+          const int rr = tid / CPR + RPP * (i0 + u);
+          const u32x4 v = *reinterpret_cast<const u32x4*>(Cs + rr * LD + c * E);
           st16_nt(Cg + off[u], epi_apply<T, BW>(p, v, in[u], bwd));
         }
       }
+    } else {
+      epi_store<T, BW, 256, BN, ROWS, LD>(tid, p, Cs, nt * BN, bwd, rows, [&](int i, size_t off, EpiIn& in) {
+        epi_load<T, BW, !YREC>(p, off, in);
+        if constexpr (YREC) in.y = *reinterpret_cast<const u32x4*>(Ys + (tid / CPR + RPP * i) * LD + (tid % CPR) * E);
+      });
     }
     if (EPASS > 1) __syncthreads();
   }
-  if constexpr (BW != 0) {
-    __syncthreads();  // the C staging area becomes the reduction buffer
-    bwd.template reduce<BN, 256>(p.bb, reinterpret_cast<float2*>(lds), tid / CPR, RPP, tid % CPR,
-                                 (size_t)blockIdx.z * p.bb.prow + mt, p.N, nt * BN);
-  }
-  if constexpr (BW != 0) {
-    if (p.fin.mode) {
-      __syncthreads();
-      bn_fin_arrive<256, BN>(p.fin, blockIdx.z * p.bb.prow + mt, nt, reinterpret_cast<double2*>(lds), &fin_flag);
-    }
-  }
+  epi_bwd_finish<T, BW, 256, BN>(tid, p, bwd, lds, blockIdx.z * p.bb.prow + mt, nt, &fin_flag);
 }
 
 // ------------------------------------------------------------------------------------------------
 // weight gradient (split over pixel ranges)
 // ------------------------------------------------------------------------------------------------
-// bf16 LDS image: rows of 256 B = 8 slots of 32 B; slot XOR swz32(row) makes the 8 rows a
-// ds_read_b64_tr_b16 half-wave touches land on 8 distinct slots.
-ARGUS_DEV int swz32(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-
+// bf16 LDS image: rows of 256 B = 8 slots of 32 B, slot XOR swz32(row) (lds_dma.h).
 // Two workgroups per CU; the 128x128 tile keeps a single staged k-step in registers (the 2-deep ring
 // would not fit two waves per SIMD without spilling; with it at one or two waves per SIMD, or as two
 // 256-thread sub-pipelines per workgroup, it measured slower: DESIGN.md §5).

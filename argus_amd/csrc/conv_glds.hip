@@ -19,27 +19,9 @@
 #include "igemm.h"
 #include "internal.h"
 #include "ktimer.h"
+#include "lds_dma.h"
 
 namespace argus {
-
-__device__ __attribute__((aligned(64))) u32x4 g_zero_page[4];  // zero-initialised (static storage)
-
-// s_waitcnt vmcnt(N) with expcnt / lgkmcnt left at their maxima (gfx9 encoding).
-template <int N> ARGUS_DEV void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
-}
-
-ARGUS_DEV void glds16(const void* src, uint32_t lds_byte_addr) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(uintptr_t)lds_byte_addr, 16, 0,
-                                   0);
-}
-
-ARGUS_DEV void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // NSTAGE 3: k-steps kt+1 and kt+2 in flight during compute(kt) (144 KB LDS for 256 x 128); 2: kt+1
 // only, 96 KB, so a workgroup fits beside one side-stream weight-gradient workgroup (64 KB) on a CU
@@ -90,26 +72,13 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) void igemm_glds_kern
   const int HWq = ph.Hq * ph.Wq;
   int a_off[AI], a_ih[AI], a_iw[AI], a_ch[AI];
   bool a_ok[AI];
-  // 1x1 / stride-1 GEMM: input pixel = GEMM row (no per-row integer divisions; igemm_kernel, conv.hip)
-  const bool a_ident = ph.K == p.Cin && ph.dh[0] == 0 && ph.dw[0] == 0 && p.ish == 1 && p.isw == 1 &&
-                       ph.Hq == p.H && ph.Wq == p.W;
+  const bool a_ident = a_rows_ident(p, &ph);  // 1x1 / stride-1 GEMM: input pixel = GEMM row
 #pragma unroll
   for (int i = 0; i < AI; ++i) {
     const int row = 8 * (i * NW + wave) + (lane >> 3);
     const int m = mt * BM + row;
     a_ok[i] = m < ph.M;
-    const int mm = a_ok[i] ? m : 0;
-    if (a_ident) {
-      a_ih[i] = 0;
-      a_iw[i] = 0;
-      a_off[i] = mm * p.lda;
-    } else {
-      const int nimg = mm / HWq, rem = mm - nimg * HWq;
-      const int qh = rem / ph.Wq, qw = rem - qh * ph.Wq;
-      a_ih[i] = qh * p.ish;
-      a_iw[i] = qw * p.isw;
-      a_off[i] = ((nimg * p.H + a_ih[i]) * p.W + a_iw[i]) * p.lda;
-    }
+    a_row_offset(p, ph, HWq, a_ok[i] ? m : 0, a_ident, a_off[i], a_ih[i], a_iw[i]);
     a_ch[i] = ((lane & 7) ^ swz8(row)) * 8;
   }
   const bf16* b_src[BI];
@@ -118,7 +87,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) void igemm_glds_kern
     const int row = 8 * (i * NW + wave) + (lane >> 3);
     b_src[i] = B + (size_t)(nt * BN + row) * p.ldb + ((lane & 7) ^ swz8(row)) * 8;
   }
-  const void* zero = (const void*)g_zero_page;
+  const void* zero = (const void*)lds_dma_zero_page;
 
   auto issue = [&](int kt, int stage) {
     const int k0 = kt * 64;
@@ -131,10 +100,10 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) void igemm_glds_kern
     for (int i = 0; i < AI; ++i) {
       const int ih = a_ih[i] + dh, iw = a_iw[i] + dw;
       const bool ok = a_ok[i] && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-      glds16(ok ? (const void*)(A + a_off[i] + tap + a_ch[i]) : zero, base + i * NW * 1024);
+      lds_dma16(ok ? (const void*)(A + a_off[i] + tap + a_ch[i]) : zero, base + i * NW * 1024);
     }
 #pragma unroll
-    for (int i = 0; i < BI; ++i) glds16(b_src[i] + boff + ci0, base + BM * 128 + i * NW * 1024);
+    for (int i = 0; i < BI; ++i) lds_dma16(b_src[i] + boff + ci0, base + BM * 128 + i * NW * 1024);
   };
 
   f32x4 acc[4][4];
@@ -172,74 +141,30 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) void igemm_glds_kern
   if constexpr (NSTAGE == 3) {  // k-steps kt+1 and kt+2 in flight during compute(kt)
     if (nk > 1) issue(1, 1);
     for (int kt = 0; kt < nk; ++kt) {
-      if (kt + 1 < nk) wait_vmcnt<GPS>(); else wait_vmcnt<0>();
-      raw_barrier();  // stage kt landed for every wave; every wave finished reading stage kt-1
+      if (kt + 1 < nk) wait_vm<GPS>(); else wait_vm<0>();
+      lds_dma_barrier();  // stage kt landed for every wave; every wave finished reading stage kt-1
       if (kt + 2 < nk) issue(kt + 2, (kt + 2) % NSTAGE);
       compute(kt % NSTAGE);
     }
   } else {  // k-step kt+1 in flight during compute(kt)
     for (int kt = 0; kt < nk; ++kt) {
-      wait_vmcnt<0>();
-      raw_barrier();  // stage kt landed for every wave; every wave finished reading stage kt-1 (= kt+1's)
+      wait_vm<0>();
+      lds_dma_barrier();  // stage kt landed for every wave; every wave finished reading stage kt-1 (= kt+1's)
       if (kt + 1 < nk) issue(kt + 1, (kt + 1) & 1);
       compute(kt & 1);
     }
   }
-  wait_vmcnt<0>();
+  wait_vm<0>();
   __syncthreads();  // LDS is reused below
 
   // ---- BN statistics per 64-row (one wave) or 128-row (two waves) tile: {sum, M2} per column ----
   if (p.stats) {
     float2* red = reinterpret_cast<float2*>(lds);  // [WM][BN]
-    int nvalid_w = ph.M - (mt * BM + wm * 64);
-    nvalid_w = nvalid_w < 0 ? 0 : (nvalid_w > 64 ? 64 : nvalid_w);
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      float s = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s += mi * 16 + g * 4 + r < nvalid_w ? acc[mi][ni][r] : 0.f;
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const float mean_w = nvalid_w > 0 ? s / (float)nvalid_w : 0.f;
-      float q = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float d = acc[mi][ni][r] - mean_w;
-          q = mi * 16 + g * 4 + r < nvalid_w ? fmaf(d, d, q) : q;
-        }
-      q += __shfl_xor(q, 16, 64);
-      q += __shfl_xor(q, 32, 64);
-      if (p.stat_tile == 64) {  // a wave's 64 rows are one partial row
-        if (lane < 16 && nvalid_w > 0)
-          store_part(p.stats + (size_t)(mt * WM + wm) * p.N + nt * BN + wn * 64 + ni * 16 + lane, make_float2(s, q));
-      } else if (lane < 16) {
-        red[wm * BN + wn * 64 + ni * 16 + lane] = make_float2(s, q);
-      }
-    }
+    bn_stats_wave<NT, BN, WM>(tid, lane, g, acc, StatRowsBelow<64>(ph.M - mt * BM, wm), p.stat_tile == 64, red, wm, wn * 64,
+                              p.stats + nt * BN, p.N, (size_t)mt);
     __syncthreads();
-    constexpr int HALVES = BM / 128;
-    if (p.stat_tile == 128)
-    for (int idx = tid; idx < HALVES * BN; idx += NT) {
-      const int h = idx / BN, col = idx - h * BN;
-      const int r0 = mt * BM + h * 128;
-      if (r0 >= ph.M) continue;
-      int na = ph.M - r0;
-      na = na > 64 ? 64 : na;
-      int nb = ph.M - (r0 + 64);
-      nb = nb < 0 ? 0 : (nb > 64 ? 64 : nb);
-      const float2 a0 = red[(2 * h) * BN + col], a1 = red[(2 * h + 1) * BN + col];
-      float m2 = a0.y + a1.y;
-      if (na > 0 && nb > 0) {
-        const float d = a0.x / (float)na - a1.x / (float)nb;
-        m2 += d * d * ((float)na * (float)nb / (float)(na + nb));
-      }
-      store_part(p.stats + (size_t)(mt * HALVES + h) * p.N + nt * BN + col, make_float2(a0.x + a1.x, m2));
-    }
-    __syncthreads();
+    bn_stats_merge<NT, BN, WM>(tid, StatRowsBelow<64>(ph.M - mt * BM, wm), p.stat_tile == 64, red, p.stats + nt * BN, p.N,
+                               (size_t)mt);
     if (p.ffin.mode) {  // the statistics finalize folded in (bnfin.h): BM / stat_tile partial rows a tile
       bn_fwd_fin_arrive<NT, BN>(p.ffin, mt, nt, reinterpret_cast<double2*>(lds), &fin_flag);
       __syncthreads();
@@ -248,66 +173,13 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) void igemm_glds_kern
 
   // ---- epilogue: stage the C tile in LDS, then 16-byte coalesced (+addend) stores ----
   bf16* Cs = reinterpret_cast<bf16*>(lds);
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wm * 64 + mi * 16 + g * 4 + r;
-        const int col = wn * 64 + ni * 16 + i16;
-        Cs[row * LD + col] = (bf16)acc[mi][ni][r];
-      }
+  epi_stage<bf16, LD>(g, i16, acc, Cs, wm * 64, wn * 64);
   __syncthreads();
-  constexpr int CPR = BN / 8;   // 16-byte chunks per row
-  constexpr int RPP = NT / CPR;  // rows per store pass
-  bf16* __restrict__ Cg = reinterpret_cast<bf16*>(p.c);
-  const int c = tid % CPR;
   BwdEpiAcc<bf16, BW> bwd;
-  if constexpr (BW != 0) bwd.init(p.bb, nt * BN + c * 8);
-  // output pixel = GEMM row (forward, stride-1 dgrad): no division per stored row
-  const bool c_ident = p.osh == 1 && p.osw == 1 && ph.oh0 == 0 && ph.ow0 == 0 && ph.Hq == p.Ho && ph.Wq == p.Wo;
-  constexpr int NIT = BM / RPP, U = 4;
-  static_assert(NIT * RPP == BM && NIT % U == 0, "epilogue row partition");
-  for (int i0 = 0; i0 < NIT; i0 += U) {
-    size_t off[U];
-    bool ok[U];
-    EpiIn in[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int rr = tid / CPR + RPP * (i0 + u);
-      const int m = mt * BM + rr;
-      ok[u] = m < ph.M;
-      const int mm = ok[u] ? m : 0;
-      if (c_ident) {
-        off[u] = (size_t)mm * p.ldc + nt * BN + c * 8;
-      } else {
-        const int nimg = mm / HWq, rem = mm - nimg * HWq;
-        const int qh = rem / ph.Wq, qw = rem - qh * ph.Wq;
-        const int oh = qh * p.osh + ph.oh0, ow = qw * p.osw + ph.ow0;
-        off[u] = (((size_t)nimg * p.Ho + oh) * p.Wo + ow) * p.ldc + nt * BN + c * 8;
-      }
-      if (ok[u]) epi_load<bf16, BW>(p, off[u], in[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (!ok[u]) continue;
-      const int rr = tid / CPR + RPP * (i0 + u);
-      const u32x4 v = *reinterpret_cast<const u32x4*>(Cs + rr * LD + c * 8);
-      st16_nt(Cg + off[u], epi_apply<bf16, BW>(p, v, in[u], bwd));
-    }
-  }
-  if constexpr (BW != 0) {
-    __syncthreads();
-    bwd.template reduce<BN, NT>(p.bb, reinterpret_cast<float2*>(lds), tid / CPR, RPP, c,
-                                (size_t)blockIdx.z * p.bb.prow + mt, p.N, nt * BN);
-  }
-  if constexpr (BW != 0) {
-    if (p.fin.mode) {
-      __syncthreads();
-      bn_fin_arrive<NT, BN>(p.fin, blockIdx.z * p.bb.prow + mt, nt, reinterpret_cast<double2*>(lds), &fin_flag);
-    }
-  }
+  if constexpr (BW != 0) bwd.init(p.bb, nt * BN + (tid % (BN / 8)) * 8);
+  epi_store<bf16, BW, NT, BN, BM, LD>(tid, p, Cs, nt * BN, bwd, EpiRows{p, ph, HWq, mt * BM, c_rows_ident(p, ph)},
+                                      [&](int, size_t off, EpiIn& in) { epi_load<bf16, BW>(p, off, in); });
+  epi_bwd_finish<bf16, BW, NT, BN>(tid, p, bwd, lds, blockIdx.z * p.bb.prow + mt, nt, &fin_flag);
 }
 
 template <int BM, int BN, int BW, int NS>

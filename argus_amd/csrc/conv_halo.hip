@@ -21,27 +21,9 @@
 #include "igemm.h"
 #include "internal.h"
 #include "ktimer.h"
+#include "lds_dma.h"
 
 namespace argus {
-
-namespace {
-
-__device__ __attribute__((aligned(64))) u32x4 halo_zero_page[4];  // zero-initialised (static storage)
-
-template <int N> ARGUS_DEV void waitvm() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
-}
-ARGUS_DEV void gl16(const void* src, uint32_t lds_byte_addr) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(uintptr_t)lds_byte_addr, 16, 0,
-                                   0);
-}
-ARGUS_DEV void sbar() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-}  // namespace
 
 constexpr int kHaloPos = 448;  // halo positions per image buffer (max (rows+2)*(W+2) over the shapes served)
 constexpr int kHaloPos1 = 416;  // single-buffer variant: 2 x (416 x 128 B + 3 x 8 KB weight stages) fit one CU
@@ -65,15 +47,6 @@ constexpr int kHaloPosDeep = 384;
 // (not 448: the fp8 shapes need no more), which leaves room for the scale images and three weight
 // stages; a wave whose last halo DMA would cover positions past 400 sends it to a 1 KB dummy slot (every
 // wave issues the same DMAs, so the counted waits hold).
-template <int N> ARGUS_DEV void waitvm_le(int n) {  // vmcnt(n) for a runtime n <= N (the next lower count)
-  if constexpr (N == 0) {
-    waitvm<0>();
-  } else {
-    if (n >= N) waitvm<N>();
-    else waitvm_le<N - 1>(n);
-  }
-}
-
 template <int BN, int BW, int HB, bool F8 = false, bool DEEP = false>
 __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_halo_kernel(const IgParams p) {
   static_assert(!DEEP || (!F8 && HB == 2 && BN == 128), "deep weight ring: the bf16 128-column double-halo form");
@@ -146,7 +119,7 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_h
     const int row = 8 * (i * NW + wave) + (lane >> 3);
     b_src[i] = Wt + (size_t)(nt * BN + row) * p.ldb * ES + ((lane & 7) ^ swz8(row)) * 16;
   }
-  const void* zero = (const void*)halo_zero_page;
+  const void* zero = (const void*)lds_dma_zero_page;
   const int nch = p.Cin / CH;
   const int nk = 9 * nch;
   // F8: the scale DMAs (4 bytes a lane): halo position qs = 64*(j*NW + wave) + lane; weight row
@@ -173,7 +146,7 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_h
     const int ci0 = cc * CH * ES;
 #pragma unroll
     for (int i = 0; i < HG; ++i)
-      gl16(h_ok[i] ? (const void*)(X + h_off[i] + ci0) : zero,
+      lds_dma16(h_ok[i] ? (const void*)(X + h_off[i] + ci0) : zero,
            (!F8 || 8 * (i * NW + wave) < HPOS) ? base + i * NW * 1024 : lds0 + DUMMY);
     if constexpr (F8) {
       const uint32_t sb = lds0 + HS_OFF + (HB == 2 ? (cc & 1) * HSB : 0);
@@ -189,7 +162,7 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_h
     const int off = (ph.boff[t] + cc * CH) * ES;
     const uint32_t base = lds0 + HB * HALO + (kt % NBS) * BST + wave * 1024;
 #pragma unroll
-    for (int i = 0; i < BG; ++i) gl16(b_src[i] + off, base + i * NW * 1024);
+    for (int i = 0; i < BG; ++i) lds_dma16(b_src[i] + off, base + i * NW * 1024);
     if constexpr (F8) {  // this wave's 16 weight rows: 4 scale bytes each (lanes >= 16 masked)
       if (lane < 16)
         __builtin_amdgcn_global_load_lds((const void*)(ws_row + off / 32),
@@ -275,6 +248,7 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_h
   // (one workgroup per CU: nothing else would hide that latency). NLD = the loads that certainly
   // issue (an addend adds more: the wait below then only waits longer).
   constexpr int CPR_ = BN / 8, NITP = 256 / (NT / CPR_);
+  static_assert(NITP * (NT / CPR_) == 256 && NITP % 4 == 0, "pre[] is indexed by epi_store's row slot: the same partition");
   // (BW 2 only, the 3x3 dgrads of the step: the mask-bit variants would spill the extra registers)
   constexpr bool PRE = BW == 2 && !F8;
   constexpr int NLD = PRE ? NITP : 0;
@@ -295,10 +269,10 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_h
       }
       const bool b_after = kt + 1 < nk;
       const bool after_pre = PRE && kt == kpre + 1;  // the prefetch went out after B(kt)
-      if (halo_after && b_after) waitvm<HGC + BGC>();
-      else if (halo_after) waitvm<HGC>();
-      else if (b_after) { if (after_pre) waitvm<BGC + NLD>(); else waitvm<BGC>(); }
-      else waitvm<0>();
+      if (halo_after && b_after) wait_vm<HGC + BGC>();
+      else if (halo_after) wait_vm<HGC>();
+      else if (b_after) { if (after_pre) wait_vm<BGC + NLD>(); else wait_vm<BGC>(); }
+      else wait_vm<0>();
     } else {
       // after B(kt): B(kt+1) .. B(kt+NBS-2) and the halos steps kt-NBS+2 .. kt-1 issued (at most one: a
       // halo goes out at tap 0 of a chunk), and the epilogue prefetch of step kpre
@@ -307,9 +281,9 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_h
 #pragma unroll
       for (int j = kt - (NBS - 2); j < kt; ++j) nh += (j >= 0 && j % 9 == 0 && j / 9 + 1 < nch) ? 1 : 0;
       const int npre = (PRE && kpre >= 0 && kt > kpre && kt <= kpre + NBS - 2) ? NLD : 0;
-      waitvm_le<(NBS - 2) * BGC + HGC + NLD>(nb * BGC + nh * HGC + npre);
+      wait_vm_le<(NBS - 2) * BGC + HGC + NLD>(nb * BGC + nh * HGC + npre);
     }
-    sbar();
+    lds_dma_barrier();
     if constexpr (PRE) {
       if (kt == kpre) {
 #pragma unroll
@@ -324,50 +298,16 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_h
     if (kt + NBS - 1 < nk) issue_b(kt + NBS - 1);
     compute(kt);
   }
-  waitvm<0>();
+  wait_vm<0>();
   __syncthreads();
 
   // ---- BN statistics (forward): one partial per 64-row wave tile or 128-row pair ----
   if (p.stats) {
-    float2* red = reinterpret_cast<float2*>(lds);
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      float s = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s += acc[mi][ni][r];
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const float mean_w = s * (1.f / 64.f);
-      float q = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float d = acc[mi][ni][r] - mean_w;
-          q = fmaf(d, d, q);
-        }
-      q += __shfl_xor(q, 16, 64);
-      q += __shfl_xor(q, 32, 64);
-      const int col = wn * 64 + ni * 16 + lane;
-      if (p.stat_tile == 64) {
-        if (lane < 16) store_part(p.stats + (size_t)(mt * 4 + wm) * p.N + nt * BN + col, make_float2(s, q));
-      } else if (lane < 16) {
-        red[wm * BN + col] = make_float2(s, q);
-      }
-    }
+    float2* red = reinterpret_cast<float2*>(lds);  // [4][BN]
+    bn_stats_wave<NT, BN, 4>(tid, lane, g, acc, StatRowsFull(), p.stat_tile == 64, red, wm, wn * 64, p.stats + nt * BN, p.N,
+                             (size_t)mt);
     __syncthreads();
-    if (p.stat_tile == 128) {
-      for (int idx = tid; idx < 2 * BN; idx += NT) {
-        const int h = idx / BN, col = idx - h * BN;
-        const float2 a0 = red[(2 * h) * BN + col], a1 = red[(2 * h + 1) * BN + col];
-        const float d = (a0.x - a1.x) * (1.f / 64.f);
-        store_part(p.stats + (size_t)(mt * 2 + h) * p.N + nt * BN + col,
-                   make_float2(a0.x + a1.x, a0.y + a1.y + d * d * 32.f));
-      }
-    }
-    __syncthreads();
+    bn_stats_merge<NT, BN, 4>(tid, StatRowsFull(), p.stat_tile == 64, red, p.stats + nt * BN, p.N, (size_t)mt);
     if (p.ffin.mode) {  // the statistics finalize folded in (bnfin.h): 256 / stat_tile partial rows a tile
       bn_fwd_fin_arrive<NT, BN>(p.ffin, mt, nt, reinterpret_cast<double2*>(lds),
                                 reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + NT * 32));
@@ -377,48 +317,19 @@ __global__ __launch_bounds__(4 * (BN / 64) * 64, HB == 1 ? 2 : 1) void conv3x3_h
 
   // ---- epilogue: LDS-staged C tile, 16-byte coalesced (+addend) stores; output pixels are contiguous ----
   bf16* Cs = reinterpret_cast<bf16*>(lds);
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        Cs[(wm * 64 + mi * 16 + g * 4 + r) * LD + wn * 64 + ni * 16 + i16] = (bf16)acc[mi][ni][r];
+  epi_stage<bf16, LD>(g, i16, acc, Cs, wm * 64, wn * 64);
   __syncthreads();
-  constexpr int CPR = BN / 8, RPP = NT / CPR;
-  bf16* __restrict__ Cg = reinterpret_cast<bf16*>(p.c);
-  const int c = tid % CPR;
   BwdEpiAcc<bf16, BW> bwd;
-  if constexpr (BW != 0) bwd.init(p.bb, nt * BN + c * 8);
-  constexpr int NIT = 256 / RPP, U = 4;
-  static_assert(NIT * RPP == 256 && NIT % U == 0 && NIT == NITP, "epilogue row partition");
-#pragma unroll
-  for (int i0 = 0; i0 < NIT; i0 += U) {
-    size_t off[U];
-    EpiIn in[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int rr = tid / CPR + RPP * (i0 + u);
-      off[u] = (size_t)slot_px(rr) * p.ldc + nt * BN + c * 8;
-      if (PRE && p.epi_pre) in[u] = pre[PRE ? i0 + u : 0];
-      else epi_load<bf16, BW>(p, off[u], in[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int rr = tid / CPR + RPP * (i0 + u);
-      const u32x4 v = *reinterpret_cast<const u32x4*>(Cs + rr * LD + c * 8);
-      st16_nt(Cg + off[u], epi_apply<bf16, BW>(p, v, in[u], bwd));
-    }
-  }
-  if constexpr (BW != 0) {
-    __syncthreads();
-    bwd.template reduce<BN, NT>(p.bb, reinterpret_cast<float2*>(lds), tid / CPR, RPP, c, (size_t)mt, p.N, nt * BN);
-  }
-  if (p.fin.mode) {  // LDS is free now: scratch [2 NT] double2, then the ticket flag
-    __syncthreads();
-    bn_fin_arrive<NT, BN>(p.fin, mt, nt, reinterpret_cast<double2*>(lds),
-                          reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + NT * 32));
-  }
+  if constexpr (BW != 0) bwd.init(p.bb, nt * BN + (tid % CPR_) * 8);
+  epi_store<bf16, BW, NT, BN, 256, LD>(
+      tid, p, Cs, nt * BN, bwd, [&](int rr, size_t& px) { px = (size_t)slot_px(rr); return true; },
+      [&](int i, size_t off, EpiIn& in) {
+        if (PRE && p.epi_pre) in = pre[PRE ? i : 0];
+        else epi_load<bf16, BW>(p, off, in);
+      });
+  // LDS is free now: scratch [2 NT] double2, then the ticket flag
+  epi_bwd_finish<bf16, BW, NT, BN, true>(tid, p, bwd, lds, mt, nt,
+                                         reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + NT * 32));
 }
 
 // the demangled instantiation name (as rocprofv3 reports it: the kernel timer's labels join the PMC summaries)
@@ -660,7 +571,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_halo_kernel(const WgHaloParam
     hx_rc[i] = ((hr - 1) << 16) | ((hc - 1) & 0xffff);
     hx_off[i] = ((ii * H + hr - 1) * W + hc - 1) * p.C + ct * 64 + ((lane & 7) ^ wsw(qq)) * 8;
   }
-  const void* zero = (const void*)halo_zero_page;
+  const void* zero = (const void*)lds_dma_zero_page;
 
   auto issue = [&](int tile, int stage) {
     int img0, r0 = 0, c0 = 0;
@@ -680,13 +591,13 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_halo_kernel(const WgHaloParam
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const bool ok = r0 + dy_lr[i] < H;
-      gl16(ok ? (const void*)(dyb + dy_off[i]) : zero, base + (wave + 8 * i) * 1024);
+      lds_dma16(ok ? (const void*)(dyb + dy_off[i]) : zero, base + (wave + 8 * i) * 1024);
     }
 #pragma unroll
     for (int i = 0; i < HP; ++i) {
       const int ih = r0 + (hx_rc[i] >> 16), iw = c0 + (int)(short)(hx_rc[i] & 0xffff);
       const bool ok = hx_in[i] && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-      gl16(ok ? (const void*)(xb + hx_off[i]) : zero, base + DYB + (wave + 8 * i) * 1024);
+      lds_dma16(ok ? (const void*)(xb + hx_off[i]) : zero, base + DYB + (wave + 8 * i) * 1024);
     }
   };
 
@@ -735,13 +646,13 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_halo_kernel(const WgHaloParam
     if (ahead == kWgStages - 1) {
       // stage (stage + 2) % 3 was last read in the previous iteration, before its closing barrier
       issue(tile + 2, stage == 0 ? 2 : stage - 1);
-      waitvm<2 * GPW>();
+      wait_vm<2 * GPW>();
     } else if (ahead == 1) {
-      waitvm<GPW>();
+      wait_vm<GPW>();
     } else {
-      waitvm<0>();
+      wait_vm<0>();
     }
-    sbar();
+    lds_dma_barrier();
     const uint32_t DYI = lds0 + stage * STG;
     const uint32_t HXI = DYI + DYB;
 #pragma unroll
@@ -762,7 +673,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_halo_kernel(const WgHaloParam
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) Mma<bf16>::run(acc[mi][ni], fa[mi], fb[ni]);
     }
-    sbar();  // every wave is done with this stage before it is refilled
+    lds_dma_barrier();  // every wave is done with this stage before it is refilled
     stage = stage == kWgStages - 1 ? 0 : stage + 1;
   }
 

@@ -23,26 +23,11 @@
 #include "igemm.h"
 #include "internal.h"
 #include "ktimer.h"
+#include "lds_dma.h"
 
 namespace argus {
 
 namespace {
-__device__ __attribute__((aligned(64))) u32x4 wgdma_zero_page[4];  // zero-initialised (static storage)
-
-ARGUS_DEV int wg_swz(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }  // = conv.hip's swz32
-
-template <int N> ARGUS_DEV void wg_waitvm() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
-}
-ARGUS_DEV void wg_gl16(const void* src, uint32_t lds_byte_addr) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(uintptr_t)lds_byte_addr, 16, 0,
-                                   0);
-}
-ARGUS_DEV void wg_bar() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 // Transposed LDS reads as inline asm (as conv_halo.hip's weight gradient): as a builtin the compiler
 // assumes it may alias the LDS-DMA stages in flight and drains them (vmcnt(0)) before the first read of
 // every k-step. The ring's counted waits and barriers order the reads; wg_tie waits for their data
@@ -58,15 +43,6 @@ template <int N> ARGUS_DEV void wg_tie(uint2 (&r)[N]) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : : "memory");
 #pragma unroll
   for (int i = 4; i < N; i += 4) asm volatile("" : "+v"(r[i]), "+v"(r[i + 1]), "+v"(r[i + 2]), "+v"(r[i + 3]));
-}
-// wait until at most `after` stages (of D DMAs per wave each) are still in flight; after <= K
-template <int K, int D> ARGUS_DEV void wg_wait_after(int after) {
-  if constexpr (K == 0) {
-    wg_waitvm<0>();
-  } else {
-    if (after >= K) wg_waitvm<K * D>();
-    else wg_wait_after<K - 1, D>(after);
-  }
 }
 }  // namespace
 
@@ -124,18 +100,18 @@ __global__ __launch_bounds__(2 * BN, BN == 256 && AP ? 1 : 2) void wgrad_dma_ker
   for (int j = 0; j < APW; ++j) {
     arow[j] = 4 * (APW * wave + j) + (lane >> 4);
     const int pos = lane & 15;
-    ach[j] = ((((pos >> 1) ^ wg_swz(arow[j])) << 1) | (pos & 1)) * 8;
+    ach[j] = ((((pos >> 1) ^ swz32(arow[j])) << 1) | (pos & 1)) * 8;
   }
 #pragma unroll
   for (int j = 0; j < BPW; ++j) {
     brow[j] = (BPW * wave + j) * (1024 / (2 * BN)) + lane / LPR;
     const int pos = lane % LPR;
-    bch[j] = ((((pos >> 1) ^ wg_swz(brow[j])) << 1) | (pos & 1)) * 8;
+    bch[j] = ((((pos >> 1) ^ swz32(brow[j])) << 1) | (pos & 1)) * 8;
   }
   // rows past the split's range read the zero page: one base pointer per operand plus a selected byte
   // offset (a select between two pointers was lowered to exec-masked branches, i.e. a varying number of
   // DMA instructions per wave, which the counted waits cannot allow)
-  const char* zero = reinterpret_cast<const char*>(wgdma_zero_page);
+  const char* zero = reinterpret_cast<const char*>(lds_dma_zero_page);
   const long dz = reinterpret_cast<const char*>(DY) - zero, yz = reinterpret_cast<const char*>(Y) - zero,
              xz = reinterpret_cast<const char*>(X) - zero;
   // G: this column tile's tap and first channel
@@ -156,8 +132,8 @@ __global__ __launch_bounds__(2 * BN, BN == 256 && AP ? 1 : 2) void wgrad_dma_ker
       const bool ok = pix < pend;
       const long a_off = 2 * ((long)pix * p.M + mt * 128 + ach[j]);
       const uint32_t la = sb + (APW * wave + j) * 1024;
-      wg_gl16(zero + (ok ? dz + a_off : 0), la);
-      if constexpr (AP) wg_gl16(zero + (ok ? yz + a_off : 0), la + AIMG);
+      lds_dma16(zero + (ok ? dz + a_off : 0), la);
+      if constexpr (AP) lds_dma16(zero + (ok ? yz + a_off : 0), la + AIMG);
     }
 #pragma unroll
     for (int j = 0; j < BPW; ++j) {
@@ -176,7 +152,7 @@ __global__ __launch_bounds__(2 * BN, BN == 256 && AP ? 1 : 2) void wgrad_dma_ker
       } else {
         x_off = 2 * ((long)pix * p.lda + ci0 + bch[j]);
       }
-      wg_gl16(zero + (ok ? xz + x_off : 0), sb + BOFF + (BPW * wave + j) * 1024);
+      lds_dma16(zero + (ok ? xz + x_off : 0), sb + BOFF + (BPW * wave + j) * 1024);
     }
   };
 
@@ -202,7 +178,7 @@ __global__ __launch_bounds__(2 * BN, BN == 256 && AP ? 1 : 2) void wgrad_dma_ker
   // LDS byte offsets of this lane's two transposed-read rows of a 16-channel block (slot)
   auto tr_addr = [&](uint32_t img, int rowbytes, int slot, int h) -> uint32_t {
     const int row = 8 * g + 4 * h + q;
-    return img + row * rowbytes + ((slot ^ wg_swz(row)) << 5) + pq * 8;
+    return img + row * rowbytes + ((slot ^ swz32(row)) << 5) + pq * 8;
   };
   auto compute = [&](int kt) {
     const uint32_t base = lds0 + (kt % NS) * STAGE;
@@ -247,15 +223,15 @@ __global__ __launch_bounds__(2 * BN, BN == 256 && AP ? 1 : 2) void wgrad_dma_ker
 
   // ring: stages of k-steps kt .. kt + NS - 2 in flight at the wait of step kt (the coefficient loads
   // drained first: the compiler cannot count past the DMAs and would drain the whole prologue for them)
-  if constexpr (AP) wg_waitvm<0>();
+  if constexpr (AP) wait_vm<0>();
   for (int kt = 0; kt < NS - 1 && kt < nk; ++kt) issue(kt);
   for (int kt = 0; kt < nk; ++kt) {
-    wg_wait_after<NS - 2, D>(min(NS - 2, nk - 1 - kt));  // stages issued after k-step kt's may fly
-    wg_bar();  // every wave's pieces of stage kt landed; stage kt - 1 is free
+    wait_vm_le<NS - 2, D>(min(NS - 2, nk - 1 - kt));  // stages issued after k-step kt's may fly
+    lds_dma_barrier();  // every wave's pieces of stage kt landed; stage kt - 1 is free
     if (kt + NS - 1 < nk) issue(kt + NS - 1);
     compute(kt);
   }
-  wg_waitvm<0>();
+  wait_vm<0>();
 
   float* out = p.part + (size_t)split * p.M * p.N;
 #pragma unroll

@@ -301,6 +301,207 @@ ARGUS_DEV u32x4 epi_apply(const IgParams& p, u32x4 v, const EpiIn& in, BwdEpiAcc
   return v;
 }
 
+// GEMM row mm of a phase -> its pixel. ident (workgroup-uniform: the pixel grid is the phase's own, stride 1,
+// no offset) skips the (image, row, column) split, whose integer divisions made the small-K 1x1 convs
+// VALU-bound. a_row_offset: the A operand's element offset and scaled row / column (the tap tests), written
+// through references in the kernels' statement order: the A rows are set up where registers are scarcest.
+// gemm_row_offset: the output pixel index of the y-recompute rows and the epilogues.
+ARGUS_DEV bool a_rows_ident(const IgParams& p, const IgPhase* ph) {  // by pointer: the tests stay branches
+  return ph->K == p.Cin && ph->dh[0] == 0 && ph->dw[0] == 0 && p.ish == 1 && p.isw == 1 && ph->Hq == p.H && ph->Wq == p.W;
+}
+ARGUS_DEV void a_row_offset(const IgParams& p, const IgPhase& ph, int HWq, int mm, bool ident, int& off, int& ih, int& iw) {
+  if (ident) {
+    ih = 0;
+    iw = 0;
+    off = mm * p.lda;
+  } else {
+    const int nimg = mm / HWq, rem = mm - nimg * HWq;
+    const int qh = rem / ph.Wq, qw = rem - qh * ph.Wq;
+    ih = qh * p.ish;
+    iw = qw * p.isw;
+    off = ((nimg * p.H + ih) * p.W + iw) * p.lda;
+  }
+}
+ARGUS_DEV bool c_rows_ident(const IgParams& p, const IgPhase& ph) {
+  return p.osh == 1 && p.osw == 1 && ph.oh0 == 0 && ph.ow0 == 0 && ph.Hq == p.Ho && ph.Wq == p.Wo;
+}
+ARGUS_DEV int gemm_row_offset(const IgParams& p, const IgPhase& ph, int HWq, int mm, bool ident) {
+  if (ident) return mm;
+  const int nimg = mm / HWq, rem = mm - nimg * HWq;
+  const int qh = rem / ph.Wq, qw = rem - qh * ph.Wq;
+  return (nimg * p.Ho + qh * p.osh + ph.oh0) * p.Wo + qw * p.osw + ph.ow0;
+}
+
+// BN-statistics partials of a C tile held as 16x16 MFMA accumulator fragments: each wave reduces its
+// rows (row mi * 16 + (lane >> 4) * 4 + r of fragment mi) to {sum, M2 about its own mean} per column;
+// per_wave stores that as partial row mt * WM + wm, otherwise waves 2h and 2h + 1 are merged (Chan) into
+// partial row mt * (WM / 2) + h. `part` points at the tile's first column of partial row 0 (row pitch N);
+// red: LDS scratch [WM][BN]; wcol: the wave's first column in the tile. Two calls with a __syncthreads()
+// between them, bn_stats_wave then bn_stats_merge (which ends with the workgroup synced); tid / lane / g are
+// the caller's values (recomputed from threadIdx they cost registers).
+// Rows is the row-validity policy:
+//   full()        every wave holds 64 valid rows (compile-time or wave-uniform): no predicates, no divisions
+//   ok(row)       the wave's accumulator row is valid
+//   wave_n()      the wave's valid rows
+//   half(h,na,nb) valid rows of waves 2h and 2h + 1; false: the half does not exist (nothing stored)
+struct StatRowsFull {  // 64-row wave tiles, all valid
+  ARGUS_DEV bool full() const { return true; }
+  ARGUS_DEV bool ok(int) const { return true; }
+  ARGUS_DEV int wave_n() const { return 64; }
+  ARGUS_DEV bool half(int, int& na, int& nb) const { na = nb = 64; return true; }
+};
+template <int WR> struct StatRowsBelow {  // WR-row wave tiles of a tile with `left` rows before the GEMM's end
+  int left, nw;
+  ARGUS_DEV static int clampw(int n) { return n < 0 ? 0 : (n > WR ? WR : n); }
+  ARGUS_DEV StatRowsBelow(int left_, int wm) : left(left_), nw(clampw(left_ - wm * WR)) {}
+  ARGUS_DEV bool full() const { return false; }
+  ARGUS_DEV bool ok(int row) const { return row < nw; }
+  ARGUS_DEV int wave_n() const { return nw; }
+  ARGUS_DEV bool half(int h, int& na, int& nb) const {
+    na = clampw(left - 2 * h * WR);
+    nb = clampw(left - (2 * h + 1) * WR);
+    return left > 2 * h * WR;
+  }
+};
+
+template <int NT, int BN, int WM, int MI, int NI, class Rows>
+ARGUS_DEV void bn_stats_wave(int tid, int lane, int g, const f32x4 (&acc)[MI][NI], const Rows& rows, bool per_wave,
+                             float2* red, int wm, int wcol, float2* part, int N, size_t mt) {
+  const int nw = rows.wave_n();
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni) {
+    float s = 0.f;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool ok = rows.ok(mi * 16 + g * 4 + r);
+        s += ok ? acc[mi][ni][r] : 0.f;
+      }
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    const float mean_w = rows.full() ? s * (1.f / 64.f) : (nw > 0 ? s / (float)nw : 0.f);
+    float q = 0.f;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool ok = rows.ok(mi * 16 + g * 4 + r);
+        const float d = acc[mi][ni][r] - mean_w;
+        q = ok ? fmaf(d, d, q) : q;
+      }
+    q += __shfl_xor(q, 16, 64);
+    q += __shfl_xor(q, 32, 64);
+    const int col = wcol + ni * 16 + lane;
+    if (per_wave) {
+      if (lane < 16 && nw > 0) store_part(part + (mt * WM + wm) * N + col, make_float2(s, q));
+    } else if (lane < 16) {
+      red[wm * BN + col] = make_float2(s, q);
+    }
+  }
+}
+// after a __syncthreads(): waves 2h and 2h + 1 of `red` -> partial row mt * (WM / 2) + h
+template <int NT, int BN, int WM, class Rows>
+ARGUS_DEV void bn_stats_merge(int tid, const Rows& rows, bool per_wave, const float2* red, float2* part, int N,
+                              size_t mt) {
+  if (!per_wave)
+    for (int idx = tid; idx < (WM / 2) * BN; idx += NT) {
+      const int h = idx / BN, col = idx - h * BN;
+      int na, nb;
+      if (!rows.half(h, na, nb)) continue;
+      const float2 a0 = red[(2 * h) * BN + col], a1 = red[(2 * h + 1) * BN + col];
+      float m2 = a0.y + a1.y;
+      if (rows.full()) {
+        const float d = (a0.x - a1.x) * (1.f / 64.f);
+        m2 += d * d * 32.f;
+      } else if (na > 0 && nb > 0) {
+        const float d = a0.x / (float)na - a1.x / (float)nb;
+        m2 += d * d * ((float)na * (float)nb / (float)(na + nb));
+      }
+      store_part(part + (mt * (WM / 2) + h) * N + col, make_float2(a0.x + a1.x, m2));
+    }
+  __syncthreads();
+}
+
+// LDS-staged C-tile epilogue, shared by igemm_kernel (conv.hip), igemm_glds_kernel and conv3x3_halo_kernel.
+// epi_stage: a wave's accumulator fragments -> Cs[row * LD + col] (row0 / col0: the wave's origin in Cs;
+// g / i16: the caller's lane >> 4 and lane & 15), through one base pointer and constant offsets.
+template <typename T, int LD, int MI, int NI>
+ARGUS_DEV void epi_stage(int g, int i16, const f32x4 (&acc)[MI][NI], T* Cs, int row0, int col0) {
+  T* dst = Cs + (row0 + g * 4) * LD + col0 + i16;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        dst[(mi * 16 + r) * LD + ni * 16] = from_f32<T>(acc[mi][ni][r]);
+}
+
+// epi_store: ROWS staged rows x BN columns -> 16-byte non-temporal stores by NT threads, thread =
+// (row tid / CPR + k * RPP, chunk tid % CPR). Per batch of U rows: every row's global operands are loaded
+// (EpiIn, see above), then applied and stored. row_px(rr, px) gives staged row rr's output pixel and
+// whether it exists; src(i, off, in) fills row-slot i's EpiIn for element offset off (epi_load, or a prefetch).
+template <typename T, int BW, int NT, int BN, int ROWS, int LD, class RowPx, class Src>
+ARGUS_DEV void epi_store(int tid, const IgParams& p, const T* Cs, int col0, BwdEpiAcc<T, BW>& bwd, RowPx&& row_px, Src&& src) {
+  constexpr int E = Chunk<T>::E, CPR = BN / E, RPP = NT / CPR;
+  constexpr int NIT = ROWS / RPP, U = NIT < 4 ? NIT : 4;
+  static_assert(NIT * RPP == ROWS && NIT % U == 0, "epilogue row partition");
+  T* __restrict__ Cg = reinterpret_cast<T*>(p.c);
+  const int c = tid % CPR;
+#pragma unroll
+  for (int i0 = 0; i0 < NIT; i0 += U) {
+    size_t off[U];
+    bool ok[U];
+    EpiIn in[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      size_t px;
+      ok[u] = row_px(tid / CPR + RPP * (i0 + u), px);
+      off[u] = px * p.ldc + col0 + c * E;
+      if (ok[u]) src(i0 + u, off[u], in[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (!ok[u]) continue;
+      const int rr = tid / CPR + RPP * (i0 + u);
+      const u32x4 v = *reinterpret_cast<const u32x4*>(Cs + rr * LD + c * E);
+      st16_nt(Cg + off[u], epi_apply<T, BW>(p, v, in[u], bwd));
+    }
+  }
+}
+
+// epi_store's row rule of the implicit GEMMs: staged row rr = GEMM row row0 + rr of the phase
+struct EpiRows {
+  const IgParams& p;
+  const IgPhase& ph;
+  int HWq, row0;
+  bool ident;  // c_rows_ident: output pixel = GEMM row (forward, stride-1 dgrad), no division per stored row
+  ARGUS_DEV bool operator()(int rr, size_t& px) const {
+    const int m = row0 + rr;
+    px = gemm_row_offset(p, ph, HWq, m < ph.M ? m : 0, ident);
+    return m < ph.M;
+  }
+};
+
+// after epi_store: the BN-backward column sums as partial row prow, then the folded finalize's ticket.
+// FIN_PLAIN: the ticket is tested without a BN-backward epilogue too (conv3x3_halo_kernel).
+template <typename T, int BW, int NT, int BN, bool FIN_PLAIN = false>
+ARGUS_DEV void epi_bwd_finish(int tid, const IgParams& p, BwdEpiAcc<T, BW>& bwd, void* lds, int prow, int nt, int* fin_flag) {
+  if constexpr (BW != 0) {
+    constexpr int CPR = BN / Chunk<T>::E;
+    __syncthreads();  // the C staging area becomes the reduction buffer
+    bwd.template reduce<BN, NT>(p.bb, reinterpret_cast<float2*>(lds), tid / CPR, NT / CPR, tid % CPR,
+                                (size_t)prow, p.N, nt * BN);
+  }
+  if constexpr (BW != 0 || FIN_PLAIN) {
+    if (p.fin.mode) {
+      __syncthreads();
+      bn_fin_arrive<NT, BN>(p.fin, prow, nt, reinterpret_cast<double2*>(lds), fin_flag);
+    }
+  }
+}
+
 // host: group plan of a folded BN-backward finalize (one partial row per (phase, row tile))
 inline void plan_fin(IgParams& p, int) {
   if (!p.fin.mode) return;

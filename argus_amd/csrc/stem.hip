@@ -138,60 +138,25 @@ __global__ __launch_bounds__(256, 3) void stem_fwd_kernel(const StemParams<T> p)
   const int vr = min(kTH, p.Ho - oh0), vc = min(kTW, p.Wo - ow0);
   const bool full = vr == kTH && vc == kTW;
   if (p.stats) {
+    if (p.counts && tid < 128 && (tid & 63) == 0)  // ragged tilings: the half-tile's pixel count (write-through)
+      store_count(p.counts + tile_lin * 2 + (tid >> 6), full ? 128 : min(max(vr - 4 * (tid >> 6), 0), 4) * vc);
+    // wave w owns tile rows 2w, 2w+1 (accumulator row = (tile row & 1) * 32 + column); halves: rows 0-3, 4-7
+    struct Rows {
+      bool all;
+      int wave, vr, vc;
+      ARGUS_DEV bool full() const { return all; }
+      ARGUS_DEV bool ok(int row) const { return all || (2 * wave + (row >> 5) < vr && (row & 31) < vc); }
+      ARGUS_DEV int wave_n() const { return min(max(vr - 2 * wave, 0), 2) * vc; }
+      ARGUS_DEV bool half(int h, int& na, int& nb) const {
+        na = min(max(vr - 4 * h, 0), 2) * vc;
+        nb = min(max(vr - 4 * h - 2, 0), 2) * vc;
+        return true;  // an empty half stores {0, 0} (its count is 0)
+      }
+    };
     float2* red = reinterpret_cast<float2*>(lds);  // [4 waves][64]
-    // this wave's tile rows 2w, 2w+1: valid pixels, and which of its accumulator rows are valid
-    const int nw = (min(max(vr - 2 * wave, 0), 2)) * vc;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      float s = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool ok = full || (2 * wave + (mi >> 1) < vr && (mi & 1) * 16 + g * 4 + r < vc);
-          s += ok ? acc[mi][ni][r] : 0.f;
-        }
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const float mean_w = full ? s * (1.f / 64.f) : (nw > 0 ? s / (float)nw : 0.f);
-      float q = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool ok = full || (2 * wave + (mi >> 1) < vr && (mi & 1) * 16 + g * 4 + r < vc);
-          const float d = acc[mi][ni][r] - mean_w;
-          q = ok ? fmaf(d, d, q) : q;
-        }
-      q += __shfl_xor(q, 16, 64);
-      q += __shfl_xor(q, 32, 64);
-      if (lane < 16) red[wave * 64 + ni * 16 + lane] = make_float2(s, q);
-    }
+    bn_stats_wave<256, 64, 4>(tid, lane, g, acc, Rows{full, wave, vr, vc}, false, red, wave, 0, p.stats, 64, tile_lin);
     __syncthreads();
-    if (tid < 128) {
-      const int h = tid >> 6, col = tid & 63;
-      const float2 a0 = red[(2 * h) * 64 + col], a1 = red[(2 * h + 1) * 64 + col];
-      float2 o;
-      if (full) {
-        const float d = (a0.x - a1.x) * (1.f / 64.f);
-        o = make_float2(a0.x + a1.x, a0.y + a1.y + d * d * 32.f);
-      } else {  // Chan's merge over the valid counts; the count goes to the row-count array
-        const int na = min(max(vr - 4 * h, 0), 2) * vc, nb = min(max(vr - 4 * h - 2, 0), 2) * vc;
-        const int n = na + nb;
-        float m2 = a0.y + a1.y;
-        if (na > 0 && nb > 0) {
-          const float d = a0.x / (float)na - a1.x / (float)nb;
-          m2 += d * d * ((float)na * (float)nb / (float)n);
-        }
-        o = n > 0 ? make_float2(a0.x + a1.x, m2) : make_float2(0.f, 0.f);
-      }
-      store_part(p.stats + (tile_lin * 2 + h) * 64 + col, o);
-      if (p.counts && col == 0) {
-        const int n = full ? 128 : (min(max(vr - 4 * h, 0), 4) * vc);
-        store_count(p.counts + tile_lin * 2 + h, n);  // write-through (the folded finalize)
-      }
-    }
-    __syncthreads();
+    bn_stats_merge<256, 64, 4>(tid, Rows{full, wave, vr, vc}, false, red, p.stats, 64, tile_lin);
     if (p.ffin.mode) {  // the statistics finalize folded in (bnfin.h): two partial rows a tile
       __shared__ int fin_flag;
       bn_fwd_fin_arrive<256, 64>(p.ffin, tile_lin, 0, reinterpret_cast<double2*>(lds), &fin_flag);

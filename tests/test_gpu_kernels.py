@@ -279,6 +279,135 @@ def test_bn_finalize_row_counts_large_mean(cuda):
     assert _rel(hv, var) < 1e-3
 
 
+def _var_without_half_merge(y, part, half):
+    """Biased variance of y (M, C; fp64) with every partial row's two halves merged WITHOUT Chan's
+    between-half term (partial rows then merged exactly): what a reduction with a wrong half merge gives."""
+    M, c = y.shape
+    key = part * 2 + half
+    nk = 2 * (int(part.max()) + 1)
+    cnt = torch.zeros(nk, dtype=torch.float64).index_add_(0, key, torch.ones(M, dtype=torch.float64))
+    s = torch.zeros(nk, c, dtype=torch.float64).index_add_(0, key, y)
+    mean_k = s / cnt.clamp_min(1.0)[:, None]
+    m2 = torch.zeros(nk, c, dtype=torch.float64).index_add_(0, key, (y - mean_k[key]) ** 2)
+    n_p, s_p, m2_p = cnt.view(-1, 2).sum(1), s.view(-1, 2, c).sum(1), m2.view(-1, 2, c).sum(1)
+    mean_p = s_p / n_p.clamp_min(1.0)[:, None]
+    return (m2_p + n_p[:, None] * (mean_p - y.mean(0)) ** 2).sum(0) / M
+
+
+def _ramp_input(half, cin, g):
+    """Small-integer input rows (M, cin): 100 on the second half of every statistics partial, 0 on the
+    first, plus noise in 0..3, so the two halves' means lie ~100 standard deviations apart."""
+    return 100.0 * half[:, None] + torch.randint(0, 4, (half.shape[0], cin), generator=g).double()
+
+
+def _select2(cout, cin):
+    """0/1 weights (cout, cin) with one or two ones a row: every output is a sum of two inputs (< 256)."""
+    w = torch.zeros(cout, cin)
+    co = torch.arange(cout)
+    w[co, co % cin] = 1.0
+    w[co, (co // 2 + 1) % cin] = 1.0
+    return w
+
+
+def _check_exact_stats(what, stats, tile, counts, y, part, half):
+    """Partial rows merged in fp64 (_merge_stats) vs fp64 statistics of the exact output y (M, C).
+    Bars: an fp32 sum of <= 128 integers below 256 is exact, an fp32 M2 over n <= 128 terms carries
+    about (n + 2) * 2^-24 = 8e-6 relative: 10x that for the variance, 1e-5 max|mean| for the mean.
+    Precondition on the inputs: leaving out the merge term of the halves moves the variance > 100 bars."""
+    M = y.shape[0]
+    mean_ref, var_ref = y.mean(0), y.var(0, unbiased=False)
+    moved = ((_var_without_half_merge(y, part, half) - var_ref).abs() / var_ref).min().item()
+    assert moved > 100 * 1e-4, (what, "inputs do not exercise the half merge", moved)
+    mean, var = _merge_stats(stats, tile, M, counts)
+    em, ev = (mean - mean_ref).abs().max().item(), ((var - var_ref).abs() / var_ref).max().item()
+    print(what, "mean err", em, "rel var err", ev, "merge term share", moved)
+    assert em <= 1e-5 * mean_ref.abs().max().item(), (what, "mean", em)
+    assert ev <= 1e-4, (what, "variance", ev)
+
+
+def test_bn_stat_partials_exact_inputs_offset_halves(cuda):
+    """The forward BN-statistics reduction (bn_stats_wave / bn_stats_merge, igemm.h) through each of its four callers on
+    inputs where Chan's merge of a partial's two halves matters: small-integer inputs and 0/1 weights make
+    every conv output an integer below 256 (exact in the fp32 accumulator and in bf16), and a ramp puts the
+    two halves of every partial ~100 standard deviations apart (the parity tests' zero-mean data leave the
+    merge term ~0, so a wrong row count in it would pass them). Cases: the register igemm (fp32 / bf16,
+    64- and 128-row tiles) with a last tile whose first half is partly valid and second empty, and one
+    whose first half is full and second partly valid (a GEMM's tail cannot leave both halves part-filled;
+    the ragged stem tile below does); the glds kernel at 64- and 128-row partials with M = 1089; the halo
+    kernel at a 64- and a 128-row partial; the LDS-patch stem on the ragged 100 x 248 frame and a full one.
+    The 64-row partials of the glds and halo kernels are single waves (the per-wave path): their two
+    32-row "halves" pin the wave's M2 about its own mean across the offset, not Chan's merge, which those
+    kernels run only at 128-row partials."""
+    from argus_amd.profiling import KernelTimer
+
+    L = lib()
+    g = torch.Generator().manual_seed(77)
+
+    def conv_case(what, kernel, dt, n, hw, cin, cout, k, tuning):
+        d, p = _desc(n, hw, hw, cin, cout, k, 1)
+        d = d.with_tuning(tuning)
+        tile = L.dll.argus_conv_fwd_stat_tile(C.byref(d), DT[dt])
+        rows = L.dll.argus_conv_fwd_stat_rows(C.byref(d), DT[dt])
+        assert tile == tuning[0], (what, tile)
+        M = n * hw * hw
+        m = torch.arange(M)
+        part, half = m // tile, (m % tile) // (tile // 2)
+        x = _ramp_input(half, cin, g)  # stride 1: GEMM row = pixel
+        w = torch.zeros(cout, k, k, cin)
+        w[:, k // 2, k // 2, :] = _select2(cout, cin)  # centre tap only
+        xd = x.view(n, hw, hw, cin).to(cuda, TDT[dt])
+        wf, _ = _prep(d, dt, w.to(cuda), cuda)
+        y = torch.empty(n, hw, hw, cout, dtype=TDT[dt], device=cuda)
+        stats = torch.full((rows, cout, 2), float("nan"), device=cuda)
+        with KernelTimer(kernel) as t:
+            L.conv_fwd(C.byref(d), DT[dt], ptr(xd), ptr(wf), ptr(y), None, None, ptr(stats), stream())
+        assert len(t.summary()) == 1, (what, "kernel", list(t.summary()))
+        ref = x @ _select2(cout, cin).double().t()
+        assert ref.max() < 256 and torch.equal(y.double().cpu().view(M, cout), ref), (what, "output not exact")
+        _check_exact_stats(what, stats.double().cpu(), tile, None, ref, part, half)
+
+    for dt in ("fp32", "bf16"):
+        # (tile, hw): M = hw^2 leaves a last tile of 41 / 97 rows (128) and 17 / 41 rows (64)
+        for tile, hw in ((128, 13), (128, 15), (64, 9), (64, 13)):
+            conv_case(("igemm", dt, tile, hw), "argus::igemm_kernel", dt, 1, hw, 64, 64, 1, {0: tile})
+    for tile in (64, 128):  # M = 1089 = 4 x 256 + 65: a last 128-row partial of 64 + 1 rows, a last 64-row one of 1
+        conv_case(("glds", tile), "argus::igemm_glds_kernel", "bf16", 1, 33, 64, 128, 1, {0: tile, 8: 64, 9: 1})
+    for tile, (cin, cout, hw, n) in ((64, HALO_SHAPES[2]), (128, HALO_SHAPES[1])):
+        conv_case(("halo", tile, hw), "argus::conv3x3_halo_kernel", "bf16", n, hw, cin, cout, 3, {0: tile, 13: 1})
+
+    # the stem: 8 x 32 output tiles, a partial = tile rows 0-3 / 4-7, its halves = tile rows (0, 1) / (2, 3)
+    for n, H, W in ((2, 100, 248), (1, 64, 128)):
+        d, p = _desc(n, H, W, 3, 64, 7, 2, stem=True)
+        tile = L.dll.argus_conv_fwd_stat_tile(C.byref(d), BF16)
+        rows = L.dll.argus_conv_fwd_stat_rows(C.byref(d), BF16)
+        assert tile == (-128 if (d.ho % 8 or d.wo % 32) else 128), (H, W, tile)
+        ni, oh, ow = torch.meshgrid(torch.arange(n), torch.arange(d.ho), torch.arange(d.wo), indexing="ij")
+        tpr = (d.wo + 31) // 32
+        tile_lin = (ni * ((d.ho + 7) // 8) + oh // 8) * tpr + ow // 32
+        part, half = (tile_lin * 2 + (oh % 8) // 4).flatten(), ((oh % 4) // 2).flatten()
+        # centre tap only (stride 2, pad 3): output pixel (oh, ow) reads input pixel (2 oh, 2 ow)
+        xo = _ramp_input(half, 3, g)
+        x4 = torch.zeros(n, H, W, 4, dtype=torch.float64)
+        x4[:, 0:2 * d.ho:2, 0:2 * d.wo:2, :3] = xo.view(n, d.ho, d.wo, 3)
+        x4 = x4.to(cuda, torch.bfloat16)
+        w = torch.zeros(64, 3, 7, 7)
+        w[:, :, 3, 3] = _select2(64, 3)
+        wmaster = w.to(cuda)
+        wf = torch.empty(64, 256, dtype=torch.bfloat16, device=cuda)
+        strides = (C.c_int64 * 4)(*wmaster.stride())
+        L.conv_weight_prep(C.byref(d), BF16, ptr(wmaster), strides, ptr(wf), None, stream())
+        y = torch.empty(n, d.ho, d.wo, 64, dtype=torch.bfloat16, device=cuda)
+        buf = torch.full((rows * 128 + rows,), float("nan"), device=cuda)  # partials (+ counts if ragged)
+        with KernelTimer("argus::stem_fwd_kernel") as t:
+            L.conv_fwd(C.byref(d), BF16, ptr(x4), ptr(wf), ptr(y), None, None, ptr(buf), stream())
+        assert len(t.summary()) == 1, ("stem kernel", H, W, list(t.summary()))
+        ref = xo @ _select2(64, 3).double().t()
+        assert ref.max() < 256 and torch.equal(y.double().cpu().view(-1, 64), ref), ("stem output not exact", H, W)
+        counts = buf[rows * 128:].view(torch.int32).cpu() if tile < 0 else None
+        _check_exact_stats(("stem", H, W), buf[:rows * 128].view(rows, 64, 2).double().cpu(), tile, counts, ref, part,
+                           half)
+
+
 def test_stem_wgrad_lds_patch_kernel(cuda):
     """bf16 stem weight gradient on the LDS-patch kernel (stem.hip: dy tile + input patch, both MFMA
     operands read pixel-major with ds_read_b64_tr_b16) vs torch's conv2d_weight and vs wgrad_kernel's
