@@ -77,6 +77,14 @@ class BnBwdPrologue(C.Structure):
                 ("dy_out", C.c_void_p)]
 
 
+class FrameSrc(C.Structure):
+    """argus_frame_src (include/argus_hip.h): where argus_stem_infer reads its frames (strides in elements)."""
+
+    _fields_ = [("base", C.c_void_p), ("in_dtype", C.c_int32), ("stride_img", C.c_int64), ("stride_c", C.c_int64),
+                ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32),
+                ("y0", C.c_int32), ("x0", C.c_int32)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _I64 = C.c_int64
@@ -168,6 +176,11 @@ SIGNATURES = {
     "argus_gelu_bwd_f32": (_I, [_I64, _P, _P, _P, _P]),
     "argus_se3_loss": (_I, [_I, _P, _P, _P, _P, _F, _P]),
     "argus_se3_exp": (_I, [_I, _P, _P, _I, _P]),
+    "argus_stem_infer": (_I, [_I, _I, _I, _I, _I, C.POINTER(FrameSrc), _P, _P, _P, _P, _P]),
+    "argus_pool_fc_gelu_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "argus_pool_fc_gelu": (_I, [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _SZ, _P]),
+    "argus_pose_tail_workspace_bytes": (_SZ, [_I, _I]),
+    "argus_pose_tail": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
     "argus_sumsq_workspace_bytes": (_SZ, [_I64]),
     "argus_global_norm": (_I, [_I64, _P, _P, _P, _P]),
     "argus_adam_step": (_I, [_I64, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P]),

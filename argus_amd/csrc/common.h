@@ -75,6 +75,11 @@ template <> ARGUS_DEV f16 from_f32<f16>(float x) {
   return (f16)(x != x ? x : c);
 }
 
+// Input pixel -> fp32: fp32 images pass through; uint8 images are divided by 255 exactly as the
+// reference's `.to(torch.float32) / 255.0` (argus/data.py:214-215), so both paths give equal bits.
+ARGUS_DEV float pixel_f32(float v) { return v; }
+ARGUS_DEV float pixel_f32(uint8_t v) { return (float)v / 255.0f; }
+
 // A 16-byte "chunk": 8 bf16 / fp16 or 4 fp32 elements. All activation and weight traffic moves in chunks.
 template <typename T> struct Chunk;
 template <> struct Chunk<float> { static constexpr int E = 4; };

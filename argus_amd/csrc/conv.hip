@@ -1155,11 +1155,6 @@ void wgrad_x3_launch(const WgParams& p, const WgPlan& pl, hipStream_t st) { disp
 // ------------------------------------------------------------------------------------------------
 // layout kernels
 // ------------------------------------------------------------------------------------------------
-// Input pixel -> fp32: fp32 images pass through; uint8 images are divided by 255 exactly as the
-// reference's `.to(torch.float32) / 255.0` (argus/data.py:214-215), so both paths give equal bits.
-ARGUS_DEV float pixel_f32(float v) { return v; }
-ARGUS_DEV float pixel_f32(uint8_t v) { return (float)v / 255.0f; }
-
 template <typename T, typename In>
 __global__ __launch_bounds__(256) void images_to_nhwc4_kernel(const In* __restrict__ x, T* __restrict__ out,
                                                               int64_t nimg, int hw) {

@@ -2,8 +2,9 @@
 // output MLP 2048->128->128->6 (models.py:58-64, GELU at :88). fp32 throughout: these GEMMs are
 // < 0.03 GFLOP/sample and latency-bound, so a simple LDS-tiled kernel on the exact
 // f32 MFMA (v_mfma_f32_16x16x4_f32) keeps the head at fp32 accuracy in every precision mode.
-#include "common.h"
+#include "bnfin.h"
 #include "internal.h"
+#include "se3.h"
 
 namespace argus {
 
@@ -153,6 +154,159 @@ __global__ void gelu_bwd_kernel(int64_t n, const float* __restrict__ x, const fl
     dx[i] = dy[i] * gelu_grad(x[i]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Frozen pose head for rows <= 16 (the deployment path: one pose per replay, latency-bound): the
+// avg-pool + resnet.fc + GELU and the output MLP + se(3) Exp in two launches, where the session had
+// avgpool_fwd, gemm_f32 (+ its split reduce), gelu and three more gemm_f32 in the graph and a clone +
+// se3_exp outside it. Both split their long reduction (2048 channels) over workgroups in slices of 64
+// channels; a slice's raw partial goes to the caller's workspace, the workgroups take bnfin.h's ticket
+// (fin_ticket<kPlainStores>), and the last arriver sums the slices in slice order (its own included), so
+// the result does not depend on which workgroup came last. Workspace: kHeadTicketBytes of ticket words
+// (zero on entry and on return), then float partials [column block][slice][row][128].
+// ------------------------------------------------------------------------------------------------
+constexpr int kHeadRows = 16;          // most rows (batch * n_cams, or batch) served
+constexpr int kHeadSlice = 64;         // reduction channels per workgroup
+constexpr int kHeadCols = 128;         // output columns per workgroup
+constexpr size_t kHeadTicketBytes = 256;
+
+// part[row][jl] = sum over the slice's 64 channels of w[j0 + jl][c0 + .] * f[row][.] for jl < 128:
+// thread (jl = tid / 2, half = tid % 2) holds its 32 weights in registers, sums them in channel order and
+// adds the two halves (lower + upper). Rows of w past `nout` are clamped and not stored.
+ARGUS_DEV void head_slice_dot(int tid, int rows, const float* __restrict__ w, int ldw, int j0, int c0, int nout,
+                              const float (*f)[kHeadSlice], float* part) {
+  const int jl = tid >> 1, half = tid & 1;
+  const int j = min(j0 + jl, nout - 1);
+  f32x4 wv[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    wv[i] = *reinterpret_cast<const f32x4*>(w + (size_t)j * ldw + c0 + half * 32 + i * 4);
+  for (int row = 0; row < rows; ++row) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s = fmaf(wv[i][e], f[row][half * 32 + i * 4 + e], s);
+    const float o = __shfl_xor(s, 1, 64);
+    if (half == 0 && j0 + jl < nout) part[row * kHeadCols + jl] = s + o;
+  }
+}
+
+// the last arriver's sum of column jl over the slices, in slice order (kLoadBatch loads in flight)
+ARGUS_DEV float head_slice_sum(const float* part, int slices, int rows, int row, int jl) {
+  float v = 0.f;
+  for (int sb = 0; sb < slices; sb += kLoadBatch) {
+    float t[kLoadBatch];
+#pragma unroll
+    for (int u = 0; u < kLoadBatch; ++u)
+      t[u] = part[((size_t)min(sb + u, slices - 1) * rows + row) * kHeadCols + jl];
+#pragma unroll
+    for (int u = 0; u < kLoadBatch; ++u) v += sb + u < slices ? t[u] : 0.f;
+  }
+  return v;
+}
+
+// grid (c / 64 slices, ceil(rdim / 128) column blocks); a ticket per column block
+template <typename T>
+__global__ __launch_bounds__(256) void pool_fc_gelu_kernel(int n, int hw, int c, const T* __restrict__ x,
+                                                           const float* __restrict__ w, const float* __restrict__ b,
+                                                           int rdim, float* __restrict__ g0, unsigned* tickets,
+                                                           float* part) {
+  constexpr int E = Chunk<T>::E, CH = kHeadSlice / E, PG = 256 / CH;  // chunks per slice row, pixel groups
+  __shared__ float feat[kHeadRows][kHeadSlice];
+  __shared__ float red[PG][kHeadSlice + 4];
+  __shared__ int flag;
+  const int tid = threadIdx.x, slice = blockIdx.x, jb = blockIdx.y, slices = gridDim.x;
+  const int c0 = slice * kHeadSlice;
+  // ---- this slice's channel means: pixel group pg sums pixels pg, pg + PG, ... in order; the groups in order ----
+  const int ch = tid % CH, pg = tid / CH;
+  for (int row = 0; row < n; ++row) {
+    float s[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) s[e] = 0.f;
+    const T* xr = x + (size_t)row * hw * c + c0 + ch * E;
+    for (int pb = pg; pb < hw; pb += PG * 4) {
+      u32x4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = ld16(xr + (size_t)min(pb + u * PG, hw - 1) * c);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float f[E];
+        ChunkCvt<T>::unpack(v[u], f);
+#pragma unroll
+        for (int e = 0; e < E; ++e) s[e] += pb + u * PG < hw ? f[e] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) red[pg][ch * E + e] = s[e];
+    __syncthreads();
+    if (tid < kHeadSlice) {
+      float t = 0.f;
+      for (int g = 0; g < PG; ++g) t += red[g][tid];
+      feat[row][tid] = t / (float)hw;
+    }
+    __syncthreads();
+  }
+  float* mine = part + ((size_t)jb * slices + slice) * n * kHeadCols;
+  head_slice_dot(tid, n, w, c, jb * kHeadCols, c0, rdim, feat, mine);
+  if (!fin_ticket<kPlainStores>(tickets + jb, (unsigned)slices, &flag)) return;
+  const float* all = part + (size_t)jb * slices * n * kHeadCols;
+  const int jl = tid & (kHeadCols - 1), j = jb * kHeadCols + jl;
+  if (j < rdim)
+    for (int row = tid >> 7; row < n; row += 2)
+      g0[(size_t)row * rdim + j] = gelu_f(head_slice_sum(all, slices, n, row, jl) + b[j]);
+}
+
+// grid d / 64 slices of output_mlp.0; the last arriver finishes the MLP and the exponential alone
+__global__ __launch_bounds__(256) void pose_tail_kernel(int batch, int d, const float* __restrict__ g0,
+                                                        const float* __restrict__ w0, const float* __restrict__ b0,
+                                                        const float* __restrict__ w2, const float* __restrict__ b2,
+                                                        const float* __restrict__ w4, const float* __restrict__ b4,
+                                                        float* __restrict__ pred, float* __restrict__ pose, int canon,
+                                                        unsigned* tickets, float* part) {
+  __shared__ float feat[kHeadRows][kHeadSlice];
+  __shared__ float h1[kHeadRows][kHeadCols], h2[kHeadRows][kHeadCols];
+  __shared__ float pr[kHeadRows * 6];
+  __shared__ int flag;
+  const int tid = threadIdx.x, slice = blockIdx.x, slices = gridDim.x;
+  for (int i = tid; i < batch * kHeadSlice; i += 256)
+    feat[i / kHeadSlice][i % kHeadSlice] = g0[(size_t)(i / kHeadSlice) * d + slice * kHeadSlice + i % kHeadSlice];
+  __syncthreads();
+  head_slice_dot(tid, batch, w0, d, 0, slice * kHeadSlice, kHeadCols, feat, part + (size_t)slice * batch * kHeadCols);
+  if (!fin_ticket<kPlainStores>(tickets, (unsigned)slices, &flag)) return;
+  const int jl = tid & (kHeadCols - 1);
+  for (int row = tid >> 7; row < batch; row += 2)  // output_mlp.0 + GELU
+    h1[row][jl] = gelu_f(head_slice_sum(part, slices, batch, row, jl) + b0[jl]);
+  __syncthreads();
+  for (int row = tid >> 7; row < batch; row += 2) {  // output_mlp.2 + GELU
+    float s = 0.f;
+    for (int k = 0; k < kHeadCols; k += 4) {
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(w2 + jl * kHeadCols + k);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s = fmaf(wv[e], h1[row][k + e], s);
+    }
+    h2[row][jl] = gelu_f(s + b2[jl]);
+  }
+  __syncthreads();
+  if (tid < batch * 6) {  // output_mlp.4
+    const int row = tid / 6, o = tid - row * 6;
+    float s = 0.f;
+    for (int k = 0; k < kHeadCols; k += 4) {
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(w4 + o * kHeadCols + k);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s = fmaf(wv[e], h2[row][k + e], s);
+    }
+    s += b4[o];
+    pr[tid] = s;
+    pred[tid] = s;
+  }
+  __syncthreads();
+  if (tid < batch) se3_exp_one(pr + tid * 6, pose + tid * 7, canon);  // argus_se3_exp's function on this pred
+}
+
+static size_t head_ws_bytes(int rows, int k, int nout) {
+  return kHeadTicketBytes + (size_t)((nout + kHeadCols - 1) / kHeadCols) * (k / kHeadSlice) * rows * kHeadCols * sizeof(float);
+}
+
 }  // namespace argus
 
 using namespace argus;
@@ -210,6 +364,72 @@ int argus_gelu_bwd_f32(int64_t count, const float* x, const float* dy, float* dx
   const int blocks = (int)std::min<int64_t>((count + 255) / 256, 4096);
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, count, x, dy, dx);
   return check_launch("gelu_bwd_kernel");
+}
+
+size_t argus_pool_fc_gelu_workspace_bytes(int n, int c, int rdim) {
+  if (n <= 0 || n > kHeadRows || c <= 0 || c % kHeadSlice || rdim <= 0) return 0;
+  return head_ws_bytes(n, c, rdim);
+}
+
+int argus_pool_fc_gelu(int x_dtype, int n, int hw, int c, const void* x, const float* w_fc, const float* b_fc, int rdim,
+                       float* g0, void* workspace, size_t workspace_bytes, argus_stream_t stream) {
+  const int dtype = x_dtype;
+  if (dtype != ARGUS_BF16 && dtype != ARGUS_F16) {
+    set_error("pool_fc_gelu: dtype must be ARGUS_BF16 or ARGUS_F16");
+    return ARGUS_ERR_ARG;
+  }
+  if (!x || !w_fc || !b_fc || !g0 || !workspace) { set_error("pool_fc_gelu: null argument"); return ARGUS_ERR_ARG; }
+  if (n <= 0 || n > kHeadRows) {
+    set_error("pool_fc_gelu: serves 1..16 rows (the deployment path; larger batches use argus_avgpool_fwd + argus_gemm_f32)");
+    return ARGUS_ERR_ARG;
+  }
+  if (hw <= 0 || rdim <= 0 || c <= 0) { set_error("pool_fc_gelu: bad sizes"); return ARGUS_ERR_ARG; }
+  if (c % kHeadSlice) { set_error("pool_fc_gelu: channels must be a multiple of 64"); return ARGUS_ERR_SHAPE; }
+  if ((int64_t)n * hw * c >= (1LL << 31)) { set_error("pool_fc_gelu: tensor exceeds 2^31 elements"); return ARGUS_ERR_SHAPE; }
+  const int jbs = (rdim + kHeadCols - 1) / kHeadCols;
+  if ((size_t)jbs * sizeof(unsigned) > kHeadTicketBytes) { set_error("pool_fc_gelu: rdim too large"); return ARGUS_ERR_SHAPE; }
+  if (workspace_bytes < head_ws_bytes(n, c, rdim)) {
+    set_error("pool_fc_gelu: workspace too small (argus_pool_fc_gelu_workspace_bytes)");
+    return ARGUS_ERR_ARG;
+  }
+  unsigned* tk = reinterpret_cast<unsigned*>(workspace);
+  float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kHeadTicketBytes);
+  const dim3 grid(c / kHeadSlice, jbs);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == ARGUS_F16)
+    hipLaunchKernelGGL(pool_fc_gelu_kernel<f16>, grid, dim3(256), 0, st, n, hw, c, (const f16*)x, w_fc, b_fc, rdim, g0, tk, part);
+  else
+    hipLaunchKernelGGL(pool_fc_gelu_kernel<bf16>, grid, dim3(256), 0, st, n, hw, c, (const bf16*)x, w_fc, b_fc, rdim, g0, tk, part);
+  return check_launch("pool_fc_gelu_kernel");
+}
+
+size_t argus_pose_tail_workspace_bytes(int batch, int d) {
+  if (batch <= 0 || batch > kHeadRows || d <= 0 || d % kHeadSlice) return 0;
+  return head_ws_bytes(batch, d, kHeadCols);
+}
+
+int argus_pose_tail(int batch, int d, const float* g0, const float* w0, const float* b0, const float* w2,
+                    const float* b2, const float* w4, const float* b4, float* pred, float* pose, int canonical_w,
+                    void* workspace, size_t workspace_bytes, argus_stream_t stream) {
+  if (!g0 || !w0 || !b0 || !w2 || !b2 || !w4 || !b4 || !pred || !pose || !workspace) {
+    set_error("pose_tail: null argument");
+    return ARGUS_ERR_ARG;
+  }
+  if (batch <= 0 || batch > kHeadRows) {
+    set_error("pose_tail: serves batch 1..16 (the deployment path; larger batches use argus_gemm_f32 + argus_se3_exp)");
+    return ARGUS_ERR_ARG;
+  }
+  if (d <= 0) { set_error("pose_tail: bad sizes"); return ARGUS_ERR_ARG; }
+  if (d % kHeadSlice) { set_error("pose_tail: d must be a multiple of 64"); return ARGUS_ERR_SHAPE; }
+  if (workspace_bytes < head_ws_bytes(batch, d, kHeadCols)) {
+    set_error("pose_tail: workspace too small (argus_pose_tail_workspace_bytes)");
+    return ARGUS_ERR_ARG;
+  }
+  unsigned* tk = reinterpret_cast<unsigned*>(workspace);
+  float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kHeadTicketBytes);
+  hipLaunchKernelGGL(pose_tail_kernel, dim3(d / kHeadSlice), dim3(256), 0, (hipStream_t)stream, batch, d, g0, w0, b0, w2,
+                     b2, w4, b4, pred, pose, canonical_w, tk, part);
+  return check_launch("pose_tail_kernel");
 }
 
 }  // extern "C"

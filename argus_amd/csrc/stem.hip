@@ -29,21 +29,10 @@
 // a workgroup stages dy (staged through the BN-backward apply when fused) and the patch once per
 // 256-pixel tile, loops over its run of tiles with the next tile's loads in flight, and writes one
 // fp32 64 x 256 partial per split for wgrad_reduce_kernel.
-#include "igemm.h"
 #include "ktimer.h"
+#include "stem_tile.h"
 
 namespace argus {
-
-namespace {
-constexpr int kTH = 8, kTW = 32;           // output tile
-constexpr int kPR = 2 * kTH + 5;           // patch rows (21)
-constexpr int kPC = 2 * kTW + 6;           // patch columns (70): column pc = input column 2*ow0 - 3 + pc
-constexpr int kWS = 7 * 32 + 8;            // LDS weight row stride, elements (224 + 8: 464 B, conflict-free)
-constexpr int kPatchB = kPR * kPC * 8;     // 11760
-constexpr int kWB = 64 * kWS * 2;          // 29696
-constexpr int kLD = 64 + 8;                // C staging row stride, elements
-constexpr int kLdsB = (kPatchB + kWB) > 256 * kLD * 2 ? (kPatchB + kWB) : 256 * kLD * 2;
-}  // namespace
 
 template <typename T>
 struct StemParams {
@@ -86,50 +75,19 @@ __global__ __launch_bounds__(256, 3) void stem_fwd_kernel(const StemParams<T> p)
     pv[i] = ok ? v : make_uint2(0u, 0u);
   }
   u32x4 wv[7];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {  // 64 rows x 28 chunks of 16 B (filter rows 0..6)
-    const int q = tid + 256 * i;
-    const int n = q / 28, ch = q - n * 28;
-    wv[i] = ld16(p.w + n * 256 + ch * 8);
-  }
+  stem_w_load(p.w, tid, wv);
 #pragma unroll
   for (int i = 0; i < (kPR * kPC + 255) / 256; ++i) {
     const int q = tid + 256 * i;
     if (q < kPR * kPC) patch[q] = pv[i];
   }
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    const int q = tid + 256 * i;
-    const int n = q / 28, ch = q - n * 28;
-    *reinterpret_cast<u32x4*>(wl + n * kWS + ch * 8) = wv[i];
-  }
+  stem_w_store(wl, tid, wv);
   __syncthreads();
 
-  // ---- MFMA: wave w owns tile rows 2w, 2w+1 (64 pixels) x 64 channels ----
+  // ---- MFMA: wave w owns tile rows 2w, 2w+1 (64 pixels) x 64 channels (stem_tile.h) ----
   const int g = lane >> 4, i16 = lane & 15;
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const uint8_t* pb = lds;
-#pragma unroll
-  for (int r = 0; r < 7; ++r) {
-    u32x4 fa[4], fb[4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      const int tr = 2 * wave + (mi >> 1), j = (mi & 1) * 16 + i16;
-      fa[mi] = *reinterpret_cast<const u32x4*>(pb + ((2 * tr + r) * kPC + 2 * j + 2 * g) * 8);
-    }
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-      fb[ni] = *reinterpret_cast<const u32x4*>(wl + (ni * 16 + i16) * kWS + r * 32 + g * 8);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        Mma<T>::run(acc[mi][ni], fa[mi], fb[ni]);
-  }
+  stem_tile_mma<T>(lds, wl, wave, lane, acc);
   __syncthreads();  // LDS is reused below
 
   // ---- BN statistics: {sum, M2} per 64-pixel wave, merged per 128-pixel half (waves 2h, 2h+1) ----
@@ -191,7 +149,6 @@ __global__ __launch_bounds__(256, 3) void stem_fwd_kernel(const StemParams<T> p)
 namespace {
 constexpr int kDyB = 256 * 128;  // dy tile: 256 pixel rows x 64 channels bf16
 constexpr int kWgLdsB = kDyB + kPatchB;
-constexpr int kPatchPT = (kPR * kPC + 255) / 256;  // patch pixels per thread (6)
 // dy row slot swizzle (4 slots of 32 B per 128-B row): the 8 rows one ds_read_b64_tr_b16 half-wave
 // touches (q = 0..3 of two 8-row groups) land on 8 distinct (row parity, slot) bank spans
 ARGUS_DEV int dswz(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }

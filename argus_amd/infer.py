@@ -46,6 +46,15 @@ class _Conv:
         self.splits, self.ws_bytes = splits, ws_bytes
 
 
+def _require_cuda(model):
+    """The model's first parameter; a model that is not on a cuda device is refused (no CPU fallback)."""
+    p0 = next(model.parameters())
+    if p0.device.type != "cuda":
+        raise RuntimeError("argus_amd.InferenceSession runs only on the MI355X HIP path: move the model to a "
+                           "cuda device (there is no CPU fallback)")
+    return p0
+
+
 class InferenceSession:
     """``session(images) -> (batch, 6)`` for a fixed ``batch`` and image size ``hw``.
 
@@ -58,10 +67,7 @@ class InferenceSession:
         if dtype not in SERVED:
             raise ValueError(f"InferenceSession serves compute_dtype 'fp32' and 'bf16' (and 'fp16' when passed "
                              f"explicitly), got {dtype!r}")
-        p0 = next(model.parameters())
-        if p0.device.type != "cuda":
-            raise RuntimeError("argus_amd.InferenceSession runs only on the MI355X HIP path: move the model to a "
-                               "cuda device (there is no CPU fallback)")
+        p0 = _require_cuda(model)
         self.model, self.device = model, p0.device
         self.batch, self.hw, self.compute_dtype, self.graph = int(batch), (int(hw[0]), int(hw[1])), dtype, bool(graph)
         self.n_cams, self.rdim = model.n_cams, model.resnet_output_dim
@@ -86,6 +92,17 @@ class InferenceSession:
         self.stem_desc = ConvDesc(N, H, W, 3, 64, 7, 7, 2, 3, H1, W1, 1)
         self.stem_wf = self._empty(64, 256)
         self.stem_coef = self._empty(2, 64, dtype=torch.float32)  # scale, shift of resnet.bn1
+        max_elems = self._plan_convs()
+        self._alloc_activations(max(max_elems, N * H1 * W1 * 64))
+        self._alloc_head()
+        self._alloc_inputs()
+        # images -> NHWC4, stem conv, max-pool, the convs, avg-pool, fc, GELU, three MLP GEMMs
+        self.launches_per_forward = 3 + len(self.convs) + 6
+
+    def _plan_convs(self) -> int:
+        """The 52 folded convs and the block schedule; returns the elements of the largest block activation."""
+        L, dt, N = self.L, self.dt, self.N
+        h, w = self.pool_hw
         self.convs: dict[str, _Conv] = {}
         self.schedule = []  # per block: (conv1, conv2, conv3, downsample | None)
 
@@ -100,8 +117,7 @@ class InferenceSession:
             self.convs[name] = cv
             return cv
 
-        h, w = H2, W2
-        max_elems = N * H1 * W1 * 64
+        max_elems = 0
         for b in resnet50_blocks():
             pf = b.prefix
             c1 = add(pf + ".conv1", pf + ".bn1", N, h, w, b.cin, b.width, 1, 1, 0)
@@ -114,14 +130,23 @@ class InferenceSession:
             max_elems = max(max_elems, N * h * w * b.cin, N * h * w * b.width, N * ho * wo * b.cout)
             h, w = ho, wo
         self.final_hw = (h, w)
+        return max_elems
+
+    def _alloc_activations(self, max_elems: int) -> None:
         # activations: the block input / output pair, a1, a2 and yd (the stem output borrows the a1 buffer)
+        N, (H, W), (H2, W2) = self.N, self.hw, self.pool_hw
         self.x0 = self._empty(N, H, W, 4)
         self.pool = [self._empty(max_elems) for _ in range(5)]
         self.amax = self._empty(N * H2 * W2 * 64, dtype=torch.uint8)
         # one split workspace for the largest request, its tickets zeroed here once (every call leaves them zero)
         self.ws = torch.zeros(max(max(cv.ws_bytes for cv in self.convs.values()), 16), dtype=torch.uint8,
                               device=self.device)
+        self.activation_bytes = (self.x0.numel() * self.x0.element_size()
+                                 + sum(t.numel() * t.element_size() for t in self.pool) + self.amax.numel())
+
+    def _alloc_head(self) -> None:
         # head (fp32), as ResNetEngine
+        L, N, B = self.L, self.N, self.batch
         D = self.n_cams * self.rdim
         f = lambda *s: self._empty(*s, dtype=torch.float32)  # noqa: E731
         self.feat, self.h0, self.g0 = f(N, 2048), f(N, self.rdim), f(B, D)
@@ -129,15 +154,14 @@ class InferenceSession:
         hws = max(L.dll.argus_gemm_f32_workspace_bytes(*s) for s in
                   [(N, self.rdim, 2048), (B, 128, D), (B, 128, 128), (B, 6, 128)])
         self.gemm_ws = self._empty(max(hws, 16), dtype=torch.uint8)
-        self.static_in = {torch.float32: f(B, 3 * self.n_cams, H, W),
-                          torch.uint8: self._empty(B, 3 * self.n_cams, H, W, dtype=torch.uint8)}
         self.head = {}
-        self.activation_bytes = (self.x0.numel() * self.x0.element_size()
-                                 + sum(t.numel() * t.element_size() for t in self.pool) + self.amax.numel()
-                                 + 4 * sum(t.numel() for t in (self.feat, self.h0, self.g0, self.h1, self.g1, self.h2,
-                                                               self.g2, self.pred)))
-        # images -> NHWC4, stem conv, max-pool, the convs, avg-pool, fc, GELU, three MLP GEMMs
-        self.launches_per_forward = 3 + len(self.convs) + 6
+        self.activation_bytes += 4 * sum(t.numel() for t in (self.feat, self.h0, self.g0, self.h1, self.g1, self.h2,
+                                                             self.g2, self.pred))
+
+    def _alloc_inputs(self) -> None:
+        B, (H, W) = self.batch, self.hw
+        self.static_in = {torch.float32: self._empty(B, 3 * self.n_cams, H, W, dtype=torch.float32),
+                          torch.uint8: self._empty(B, 3 * self.n_cams, H, W, dtype=torch.uint8)}
 
     def refresh(self) -> None:
         """Re-fold from the model's current parameters and buffers (reads the model, never writes it)."""

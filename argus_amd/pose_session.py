@@ -1,0 +1,206 @@
+"""Frozen pose session: camera frames in, SE(3) pose out, in one replayed graph.
+
+``PoseSession`` is an ``InferenceSession`` whose two ends are fused for the deployment case (one pose per
+replay, ``batch * n_cams <= 16``, bf16 or fp16):
+
+- front: ``argus_stem_infer`` reads the frames as they arrive (planar ``(B, 3*n_cams, Hs, Ws)`` or interleaved
+  ``(B, n_cams, Hs, Ws, 3)``, uint8 or fp32, center-cropped on the fly) and writes the pooled stem output in one
+  launch: no NHWC4 copy, no stem output round trip, no argmax, no host-side transpose / crop
+  (argus/validate_real.py:58-75);
+- back: ``argus_pool_fc_gelu`` + ``argus_pose_tail`` replace avg-pool, fc, GELU, the three MLP GEMMs and the
+  se(3) exponential, so the replay itself ends in the pose (``get_pose``, argus/utils.py:179-189).
+
+The graph is stem-infer, the 52 folded convs, pool-fc-gelu, pose-tail: 55 launches where the parent session has
+61 in the graph and two more behind it. ``fused_stem=False`` / ``fused_head=False`` put the parent's launches
+back for that end (A/B timing; bisecting a mismatch to one end). Everything else (``refresh()``, the fp16 range
+check, snapshot semantics) is inherited.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from argus_amd._lib import FrameSrc, ptr, stream
+from argus_amd.data import center_crop_slices
+from argus_amd.infer import InferenceSession, _require_cuda
+from argus_amd.models import NCameraCNN
+from argus_amd.utils import se3_exp
+
+MAX_ROWS = 16  # argus_pool_fc_gelu / argus_pose_tail serve batch * n_cams <= 16
+
+
+class PoseSession(InferenceSession):
+    """``session.pose(frames) -> (batch, 7)`` and ``session(frames) -> (batch, 6)`` from one replay.
+
+    ``hw``: the size the network sees; ``frame_hw``: the size of the frames handed in (default ``hw``), center
+    cropped to ``hw`` as kornia does (``data.center_crop_slices``). ``layout``: "chw" for ``(B, 3*n_cams, Hs,
+    Ws)``, "hwc" for ``(B, n_cams, Hs, Ws, 3)``. ``session.frames[dtype]`` are the static input buffers (uint8 and
+    float32): ``pose(None)`` replays on what the caller wrote there."""
+
+    def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
+                 graph: bool = True, frame_hw: tuple | None = None, layout: str = "chw", fused_stem: bool = True,
+                 fused_head: bool = True):
+        _require_cuda(model)
+        dtype = model.compute_dtype if compute_dtype is None else compute_dtype
+        if dtype not in ("bf16", "fp16"):
+            raise ValueError(f"PoseSession serves compute_dtype 'bf16' and 'fp16', got {dtype!r}: use "
+                             f"InferenceSession for 'fp32'")
+        if int(batch) * model.n_cams > MAX_ROWS:
+            raise ValueError(f"PoseSession serves batch * n_cams <= {MAX_ROWS} (the deployment path), got "
+                             f"{int(batch) * model.n_cams}: use InferenceSession for larger batches")
+        if layout not in ("chw", "hwc"):
+            raise ValueError(f"PoseSession layout is 'chw' or 'hwc', got {layout!r}")
+        self.frame_hw = (int(hw[0]), int(hw[1])) if frame_hw is None else (int(frame_hw[0]), int(frame_hw[1]))
+        self.layout, self.fused_stem, self.fused_head = layout, bool(fused_stem), bool(fused_head)
+        if self.frame_hw[0] < hw[0] or self.frame_hw[1] < hw[1]:
+            raise ValueError(f"PoseSession: frame_hw {self.frame_hw} is smaller than hw {tuple(hw)}")
+        if not self.fused_stem and (layout != "chw" or self.frame_hw != (int(hw[0]), int(hw[1]))):
+            raise ValueError("PoseSession(fused_stem=False) takes pre-cropped 'chw' frames only: the 'hwc' layout "
+                             "and the crop are argus_stem_infer's")
+        ys, xs = center_crop_slices(self.frame_hw, hw)
+        self.crop = (ys.start, xs.start)
+        super().__init__(model, batch, hw, dtype, graph)
+
+    # ------------------------------------------------------------------ construction
+    def _plan(self) -> None:
+        super()._plan()
+        self.launches_per_forward = (1 if self.fused_stem else 3) + len(self.convs) + (2 if self.fused_head else 6)
+
+    def _alloc_activations(self, max_elems: int) -> None:
+        if not self.fused_stem:
+            return super()._alloc_activations(max_elems)
+        # no NHWC4 copy, no stem output, no argmax: the pooled stem output is the first block's input
+        N, (H2, W2) = self.N, self.pool_hw
+        blocks = max(N * H2 * W2 * 64, self._block_elems)
+        self.pool = [self._empty(blocks) for _ in range(5)]
+        self.ws = torch.zeros(max(max(cv.ws_bytes for cv in self.convs.values()), 16), dtype=torch.uint8,
+                              device=self.device)
+        self.activation_bytes = sum(t.numel() * t.element_size() for t in self.pool)
+
+    def _plan_convs(self) -> int:
+        self._block_elems = super()._plan_convs()
+        return self._block_elems
+
+    def _alloc_head(self) -> None:
+        super()._alloc_head()
+        L, N, B, D = self.L, self.N, self.batch, self.n_cams * self.rdim
+        self.pose_out = self._empty(B, 7, dtype=torch.float32)
+        # ticket words zeroed here once; every launch leaves them zero
+        self.fc_ws = torch.zeros(L.dll.argus_pool_fc_gelu_workspace_bytes(N, 2048, self.rdim), dtype=torch.uint8,
+                                 device=self.device)
+        self.tail_ws = torch.zeros(L.dll.argus_pose_tail_workspace_bytes(B, D), dtype=torch.uint8, device=self.device)
+        if not self.fc_ws.numel() or not self.tail_ws.numel():
+            raise RuntimeError(f"argus_pool_fc_gelu / argus_pose_tail do not serve rows {N}, rdim {self.rdim}")
+
+    def _alloc_inputs(self) -> None:
+        B, n, (Hs, Ws) = self.batch, self.n_cams, self.frame_hw
+        shape = (B, 3 * n, Hs, Ws) if self.layout == "chw" else (B, n, Hs, Ws, 3)
+        self.frames = {dt: self._empty(*shape, dtype=dt) for dt in (torch.float32, torch.uint8)}
+        self.static_in = self.frames
+        self._src = {}
+        for dt, t in self.frames.items():
+            st = (3 * Hs * Ws, Hs * Ws, Ws, 1) if self.layout == "chw" else (3 * Hs * Ws, 1, 3 * Ws, 3)
+            self._src[dt] = FrameSrc(ptr(t), 0 if dt == torch.uint8 else 1, *st, Hs, Ws, *self.crop)
+
+    # ------------------------------------------------------------------ forward
+    def _forward(self, x: torch.Tensor, probe=None) -> torch.Tensor:
+        """The launches of one forward from the static frame buffer ``x`` into self.pred and self.pose_out."""
+        if not self.fused_stem:
+            return super()._forward(x, probe)
+        L, dt, s, N = self.L, self.dt, stream(), self.N
+        H, W = self.hw
+        _, h, blocks = self._buffers()
+        L.stem_infer(dt, N, H, W, 64, C.byref(self._src[x.dtype]), ptr(self.stem_wf), ptr(self.stem_coef[0]),
+                     ptr(self.stem_coef[1]), ptr(h), s)
+        if probe is not None:
+            probe(h, N * self.pool_hw[0] * self.pool_hw[1] * 64)
+        for (c1, c2, c3, ds), (a1, a2, out, yd) in zip(self.schedule, blocks):
+            self._conv(c1, h, a1, None, 1, s, probe)
+            self._conv(c2, a1, a2, None, 1, s, probe)
+            res = h
+            if ds is not None:
+                self._conv(ds, h, yd, None, 0, s, probe)
+                res = yd
+            self._conv(c3, a2, out, res, 1, s, probe)
+            h = out
+        return self._head(h)
+
+    def _head(self, h: torch.Tensor) -> torch.Tensor:
+        if not self.fused_head:
+            return super()._head(h)
+        L, s, N, B = self.L, stream(), self.N, self.batch
+        hf, wf = self.final_hw
+        hd, D = self.head, self.n_cams * self.rdim
+        L.pool_fc_gelu(self.dt, N, hf * wf, 2048, ptr(h), ptr(hd["resnet.fc", "weight"]), ptr(hd["resnet.fc", "bias"]),
+                       self.rdim, ptr(self.g0), ptr(self.fc_ws), self.fc_ws.numel(), s)
+        L.pose_tail(B, D, ptr(self.g0), ptr(hd["output_mlp.0", "weight"]), ptr(hd["output_mlp.0", "bias"]),
+                    ptr(hd["output_mlp.2", "weight"]), ptr(hd["output_mlp.2", "bias"]),
+                    ptr(hd["output_mlp.4", "weight"]), ptr(hd["output_mlp.4", "bias"]), ptr(self.pred),
+                    ptr(self.pose_out), 0, ptr(self.tail_ws), self.tail_ws.numel(), s)
+        return self.pred
+
+    def _check_images(self, images, who: str) -> None:
+        want = tuple(self.frames[torch.uint8].shape)
+        name = f"{type(self).__name__}.{who}"
+        if not isinstance(images, torch.Tensor) or tuple(images.shape) != want:
+            raise ValueError(f"{name} expects {self.layout!r} frames of shape {want}, got "
+                             f"{tuple(images.shape) if isinstance(images, torch.Tensor) else type(images).__name__}")
+        if images.dtype not in self.frames:
+            raise ValueError(f"{name} expects float32 or uint8 frames, got {images.dtype}")
+
+    def _replay(self, frames, dtype=None) -> None:
+        """One forward on ``frames`` (copied into the static buffer of their dtype), or with ``frames`` None on
+        what ``self.frames[dtype]`` holds (default: uint8)."""
+        if frames is None:
+            dtype = torch.uint8 if dtype is None else dtype
+        else:
+            self._check_images(frames, "pose")
+            dtype = frames.dtype
+        x = self.frames[dtype]
+        with torch.cuda.device(self.device), torch.no_grad():
+            if frames is not None:
+                x.copy_(frames)
+            if not self.graph:
+                self._forward(x)
+                return
+            g = self._graphs.get(("forward", dtype))
+            if g is None:
+                side = torch.cuda.Stream(self.device)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):  # untimed warm-up outside the capture
+                    self._forward(x)
+                torch.cuda.current_stream().wait_stream(side)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._forward(x)
+                self._graphs["forward", dtype] = g
+            g.replay()
+
+    def __call__(self, frames: torch.Tensor | None, dtype=None) -> torch.Tensor:
+        """frames (fp32 in [0, 1] or uint8 in [0, 255]) -> (batch, 6) se(3), a fresh tensor."""
+        self._replay(frames, dtype)
+        return self.pred.clone()
+
+    def pose(self, frames: torch.Tensor | None, dtype=None) -> torch.Tensor:
+        """(batch, 7) [t, qx, qy, qz, qw], a fresh tensor: written by the replay itself (``fused_head``), else
+        ``utils.se3_exp`` of the prediction as the parent session."""
+        self._replay(frames, dtype)
+        if not self.fused_head:
+            return se3_exp(self.pred.clone())
+        return self.pose_out.clone()
+
+    def activation_peak(self, frames: torch.Tensor) -> float:
+        """As the parent's, with the pooled stem output probed in place of the stem output (which no longer
+        exists): the largest |activation| of one eager forward of ``frames``."""
+        self._check_images(frames, "activation_peak")
+        peak = torch.zeros((), dtype=torch.float32, device=self.device)
+
+        def probe(buf, elements):
+            torch.maximum(peak, buf[:elements].abs().max().float(), out=peak)
+
+        with torch.cuda.device(self.device), torch.no_grad():
+            x = self.frames[frames.dtype]
+            x.copy_(frames)
+            self._forward(x, probe)
+        return float(peak.item())

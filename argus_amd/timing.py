@@ -2,6 +2,7 @@
 
     python -m argus_amd.timing [--trials 100] [--batch 2] [--hw 256 256] [--dtype fp32|bf16x3|bf16]
                                [--eval] [--no-graph] [--frozen [--dtype fp16]]
+    python -m argus_amd.timing --frozen --pose [--layout hwc --frame-hw Hs Ws] [--parent]
     python -m argus_amd.timing --input-grad [--out profiles/input_grad.txt]
 
 Reference semantics (scripts/timing.py:10-48): ``NCameraCNN(n_cams=2)`` in fp32 on the GPU, left in
@@ -94,6 +95,53 @@ def forward_latency(trials: int = 100, batch: int = 2, hw=(256, 256), dtype: str
     if frozen:
         r["frozen"] = True
     return r
+
+
+def pose_latency(trials: int = 200, batch: int = 1, hw=(256, 256), dtype: str = "bf16", graph: bool = True,
+                 layout: str = "chw", frame_hw=None, fused_stem: bool = True, fused_head: bool = True,
+                 parent: bool = False, device: str = "cuda") -> dict:
+    """Mean / median / min seconds of one ``pose()`` call, from uint8 frames on the device to the (batch, 7) pose
+    tensor, over ``trials`` timed trials. ``parent``: the yardstick arm, ``InferenceSession.pose()`` on the same
+    frames (an "hwc" layout or a crop is brought to the planar cropped tensor it needs with torch ops first, as
+    argus/validate_real.py:58-75 does); else a ``PoseSession`` with the given switches."""
+    from argus_amd.data import center_crop_slices
+    from argus_amd.infer import InferenceSession
+    from argus_amd.pose_session import PoseSession
+
+    torch.manual_seed(0)
+    cfg = NCameraCNNConfig(n_cams=2)
+    model = NCameraCNN(cfg, compute_dtype="fp32" if dtype == "fp16" else dtype).to(device).eval()
+    H, W = hw
+    Hs, Ws = (H, W) if frame_hw is None else frame_hw
+    shape = (batch, 3 * cfg.n_cams, Hs, Ws) if layout == "chw" else (batch, cfg.n_cams, Hs, Ws, 3)
+    if parent:
+        session = InferenceSession(model, batch, (H, W), compute_dtype=dtype, graph=graph)
+        ys, xs = center_crop_slices((Hs, Ws), (H, W))
+
+        def run(x):
+            if layout == "hwc":
+                x = x.permute(0, 1, 4, 2, 3).reshape(batch, 3 * cfg.n_cams, Hs, Ws)
+            if (Hs, Ws) != (H, W):
+                x = x[..., ys, xs]
+            return session.pose(x)
+    else:
+        session = PoseSession(model, batch, (H, W), compute_dtype=dtype, graph=graph, frame_hw=(Hs, Ws), layout=layout,
+                              fused_stem=fused_stem, fused_head=fused_head)
+        run = session.pose
+    times, first = [], None
+    for i in range(trials + 1):
+        x = torch.randint(0, 256, shape, dtype=torch.uint8, device=device)
+        out, t = time_torch_fn(lambda: run(x))
+        if i == 0:
+            first = t
+        else:
+            times.append(t)
+    assert torch.isfinite(out).all() and tuple(out.shape) == (batch, 7)
+    return {"mean_s": statistics.fmean(times), "median_s": statistics.median(times), "min_s": min(times),
+            "first_call_s": first, "trials": trials, "batch": batch, "hw": list(hw), "frame_hw": [Hs, Ws],
+            "layout": layout, "dtype": dtype, "graph": graph, "pose": True,
+            "arm": "InferenceSession" if parent else f"PoseSession(stem={int(fused_stem)},head={int(fused_head)})",
+            "launches_per_forward": session.launches_per_forward}
 
 
 def _event_ms(fn, reps: int) -> float:
@@ -223,7 +271,22 @@ def main(argv=None) -> None:
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a replayed hipGraph")
     ap.add_argument("--frozen", action="store_true",
                     help="time an InferenceSession of the eval-mode model (fp32 / bf16 / fp16)")
+    ap.add_argument("--pose", action="store_true",
+                    help="with --frozen: time PoseSession.pose() end to end (uint8 frames in, pose out)")
+    ap.add_argument("--layout", default="chw", choices=["chw", "hwc"], help="--pose: the frames' layout")
+    ap.add_argument("--frame-hw", type=int, nargs=2, default=None, help="--pose: frame size, center-cropped to --hw")
+    ap.add_argument("--unfused-stem", action="store_true", help="--pose: the parent session's three stem launches")
+    ap.add_argument("--unfused-head", action="store_true", help="--pose: the parent session's head launches")
+    ap.add_argument("--parent", action="store_true", help="--pose: time InferenceSession.pose() instead (yardstick)")
     a = ap.parse_args(argv)
+    if a.pose:
+        if not a.frozen:
+            ap.error("--pose times a frozen session: pass --frozen")
+        r = pose_latency(a.trials, a.batch, tuple(a.hw), a.dtype, not a.no_graph, a.layout,
+                         tuple(a.frame_hw) if a.frame_hw else None, not a.unfused_stem, not a.unfused_head, a.parent)
+        print(f"pose() took {r['mean_s']} seconds on average.")
+        print(json.dumps(r))
+        return
     if a.dtype == "fp16" and not a.frozen:
         ap.error("--dtype fp16 is served by --frozen only")
     if a.input_grad:

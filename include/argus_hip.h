@@ -43,7 +43,8 @@ typedef void* argus_stream_t; /* hipStream_t */
  *   argus_conv_weight_prep (stem descriptor only: writes w_fwd, ignores w_dgrad),
  *   argus_conv_fwd (stem descriptor only, scale = shift = stat_part = NULL),
  *   argus_maxpool_fwd, argus_avgpool_fwd, argus_conv_fold_bn,
- *   argus_conv_infer, argus_conv_infer_splits, _max_splits, _workspace_bytes.
+ *   argus_conv_infer, argus_conv_infer_splits, _max_splits, _workspace_bytes,
+ *   argus_stem_infer, argus_pool_fc_gelu (and argus_pose_tail, which is fp32 and takes no dtype).
  * Every other entry point that takes a dtype rejects it before anything is launched: the launching ones
  * return ARGUS_ERR_ARG, the planning queries their "not served" value (0, or -1 where that is their error),
  * and argus_last_error() names the dtype. There is no fp16 training path. */
@@ -566,6 +567,58 @@ int argus_se3_loss(int batch, const float* pred, const float* target, float* los
 /* se(3) -> SE(3) exponential (pypose se3.Exp; get_pose, argus/utils.py:179-189): out (B,7) =
  * [t, qx, qy, qz, qw]; canonical_w != 0 flips q to w >= 0. */
 int argus_se3_exp(int batch, const float* xi, float* out, int canonical_w, argus_stream_t stream);
+
+/* ---- frozen pose session: the two ends of the forward fused (PoseSession, argus_amd/pose_session.py) ---- */
+/* Where argus_stem_infer reads its frames. Channel c of pixel (y, x) of image i is element
+ * base[i*stride_img + c*stride_c + (y0 + y)*stride_y + (x0 + x)*stride_x] (strides in elements, >= 0; within
+ * one image the offsets from the crop origin must fit 31 bits). Planar (B, 3*n_cams, H, W): stride_img = 3*H*W,
+ * stride_c = H*W, stride_y = W, stride_x = 1. Interleaved camera frames (B, n_cams, Hs, Ws, 3): stride_img =
+ * 3*Hs*Ws, stride_c = 1, stride_y = 3*Ws, stride_x = 3, with (y0, x0) the crop origin. */
+typedef struct {
+  const void* base;
+  int32_t in_dtype; /* 0 uint8 (v / 255), 1 fp32 */
+  int64_t stride_img, stride_c, stride_y, stride_x;
+  int32_t src_h, src_w; /* the source frame; y0 + h <= src_h and x0 + w <= src_w are checked */
+  int32_t y0, x0;       /* crop origin */
+} argus_frame_src;
+
+/* out[n][ph][pw][k] = T(max over the 3x3 / stride 2 / pad 1 window of relu(conv7x7s2p3(x)[..][k] * scale[k] +
+ * shift[k])): resnet.conv1 -> bn1.eval() -> relu -> maxpool (torchvision resnet.py; argus/models.py:84) in one
+ * launch, from the frames as the camera delivers them: replaces the `.permute(0, 3, 1, 2)` + `cat` + center
+ * crop of argus/validate_real.py:58-75 and, in a frozen session, argus_images[_u8]_to_nhwc4 + argus_conv_fwd
+ * (stem) + argus_maxpool_fwd. A pixel becomes T(v) (uint8: T(v / 255.0f)), the bits argus_images_to_nhwc4
+ * stores; w_fwd is argus_conv_weight_prep's padded stem copy [64][8][8][4]; scale / shift (fp32,
+ * argus_bn_eval_coeffs) are applied to the fp32 accumulator and the result is rounded to T once. out:
+ * (n_img, H2, W2, 64) NHWC with H1 = (h - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1. out_dtype (T; the frames have
+ * their own in_dtype) is ARGUS_BF16 or ARGUS_F16
+ * (ARGUS_F32, ARGUS_FP8 and unknown values: ARGUS_ERR_ARG, "dtype" in the message); k = 64; h, w >= 8. Nothing
+ * allocates or synchronises (graph-capturable); every bad argument is refused before a launch. */
+int argus_stem_infer(int out_dtype, int n_img, int h, int w, int k, const argus_frame_src* src, const void* w_fwd,
+                     const float* scale, const float* shift, void* out, argus_stream_t stream);
+
+/* g0[n][j] = gelu(b_fc[j] + sum_c w_fc[j][c] * mean_p x[n][p][c]): avgpool + resnet.fc + the nn.GELU() of
+ * argus/models.py:85-88 in one launch (replaces argus_avgpool_fwd + argus_gemm_f32 (+ its split reduce) +
+ * argus_gelu_f32 of a frozen session). x (n, hw, c) of x_dtype (ARGUS_BF16 or ARGUS_F16; anything else
+ * ARGUS_ERR_ARG, "dtype"), w_fc (rdim, c) / b_fc / g0 (n, rdim) fp32, fp32 arithmetic. n <= 16 (more:
+ * ARGUS_ERR_ARG: this is the deployment path), c a multiple of 64. The reduction over c is split over
+ * workgroups in slices of 64 channels, summed in slice order by the last to arrive: bit-reproducible. The
+ * workspace (argus_pool_fc_gelu_workspace_bytes; 0 = not served) starts with 256 bytes of ticket words that
+ * must be zero on entry and are zero again on return (zero the buffer once); one sized for the largest n
+ * serves every smaller n. */
+size_t argus_pool_fc_gelu_workspace_bytes(int n, int c, int rdim);
+int argus_pool_fc_gelu(int x_dtype, int n, int hw, int c, const void* x, const float* w_fc, const float* b_fc, int rdim,
+                       float* g0, void* workspace, size_t workspace_bytes, argus_stream_t stream);
+
+/* The output MLP and the exponential in one launch: pred = output_mlp.4(gelu(output_mlp.2(gelu(output_mlp.0(g0)))))
+ * (argus/models.py:58-64, 89-90; w0 (128, d), w2 (128, 128), w4 (6, 128), all fp32) and pose = se3.Exp(pred)
+ * (get_pose, argus/utils.py:179-189): replaces three argus_gemm_f32 and argus_se3_exp. output_mlp.0's
+ * reduction over d (a multiple of 64) is split over workgroups like argus_pool_fc_gelu's; the last arriver
+ * finishes alone. pred (batch, 6); pose (batch, 7) [t, qx, qy, qz, qw], bit-identical to argus_se3_exp of that
+ * pred (the same device function). batch <= 16 (more: ARGUS_ERR_ARG). Workspace as argus_pool_fc_gelu's. */
+size_t argus_pose_tail_workspace_bytes(int batch, int d);
+int argus_pose_tail(int batch, int d, const float* g0, const float* w0, const float* b0, const float* w2,
+                    const float* b2, const float* w4, const float* b4, float* pred, float* pose, int canonical_w,
+                    void* workspace, size_t workspace_bytes, argus_stream_t stream);
 
 /* ---- photometric training augmentations (argus/data.py:41-103; csrc/augment.hip) -------------
  * src: uint8 images (n_img, 3, H, W) planar (a B x 6 x H x W sample batch is 2B such images);
