@@ -113,6 +113,9 @@ SIGNATURES = {
     "argus_conv_fold_bn_dgrad": (_I, [_DESC, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
     "argus_conv_infer_dgrad_plan": (_I, [_DESC, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_SZ)]),
     "argus_conv_infer_dgrad": (_I, [_DESC, _I, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+    "argus_bias_grad_plan": (_I, [_I, _I64, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_SZ)]),
+    "argus_bias_grad": (_I, [_I, _I64, _I, _P, _P, _I, _P, _SZ, _P]),
+    "argus_conv_fold_bn_bwd": (_I, [_DESC, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P]),
     "argus_conv_x8_ok": (_I, [_DESC, _I]),
     "argus_conv_fwd_stats_only_rows": (_I, [_DESC, _I]),
     "argus_conv_fwd_stats_only_tile": (_I, [_DESC, _I]),

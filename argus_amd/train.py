@@ -9,6 +9,10 @@ train over the loader, print the mean train loss, validate (eval mode, running B
 ReduceLROnPlateau(patience 5, factor 0.5) on the validation loss, save ``{run_id}.pth`` =
 ``model.state_dict()`` (reference keys / OIHW shapes) on rank 0 every ``save_epochs``.
 
+Extensions for adapting a trained checkpoint: ``--init-checkpoint PATH`` loads a state_dict before training and
+``--freeze-bn`` replaces the train-mode step by ``argus_amd.finetune.FineTuneSession.step`` (the model stays in eval
+mode, the running statistics are used and never written; single process).
+
 The step itself is ``argus_amd.step.FusedTrainer`` (HIP kernels end to end, flat-buffer RCCL
 all-reduce + clip + Adam) instead of autograd + DDP. ``--amp`` selects the bf16 kernels (the
 reference's fp16 autocast; no GradScaler is needed in bf16). ``--multigpu``: one process per GPU —
@@ -91,9 +95,17 @@ class TrainConfig:
     # extension (--resident-dataset): decode the dataset once into device memory and build every batch there
     # (argus_amd.resident: index gather + occluder arcs in one HIP launch) instead of the DataLoader workers
     resident_dataset: bool = False
+    # extension (--init-checkpoint PATH): load this state_dict (module. / _orig_mod. prefixes stripped) before training
+    init_checkpoint: Optional[str] = None
+    # extension (--freeze-bn): fine-tune the eval-mode function (argus_amd.finetune.FineTuneSession): the model
+    # stays in eval mode, BatchNorm uses and keeps its running statistics, only the parameters move
+    freeze_bn: bool = False
 
     def __post_init__(self) -> None:
         assert isinstance(self.save_dir, str)
+        if self.freeze_bn and self.multigpu:
+            raise ValueError("--freeze-bn is single-process: frozen-BatchNorm fine-tuning is not data-parallel "
+                             "(drop --multigpu)")
         if self.float32_matmul_precision not in ("highest", "high"):
             raise ValueError(f"float32_matmul_precision must be 'highest' or 'high', got "
                              f"{self.float32_matmul_precision!r}")
@@ -234,11 +246,20 @@ def initialize_training(cfg: TrainConfig, rank: int = 0, world: int = 1):
 
     fp32_mode = "bf16x3" if cfg.float32_matmul_precision == "high" else "fp32"
     model = NCameraCNN(cfg.model_config, compute_dtype="bf16" if cfg.amp else fp32_mode).to(device)
+    if cfg.init_checkpoint is not None:
+        from argus_amd.models import strip_checkpoint_prefixes
+
+        model.load_state_dict(strip_checkpoint_prefixes(torch.load(cfg.init_checkpoint, map_location=device)))
     if distributed:  # DDP's constructor broadcast (train.py:199): every rank starts from rank 0's weights
         for t in list(model.parameters()) + list(model.buffers()):
             dist.broadcast(t.data, src=0)
         model.invalidate_bn_counters()
-    trainer = FusedTrainer(model, lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm)
+    if cfg.freeze_bn:  # one FineTuneSession per batch size met, behind FusedTrainer's step / lr
+        from argus_amd.finetune import FrozenTrainer
+
+        trainer = FrozenTrainer(model.eval(), lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm)
+    else:
+        trainer = FusedTrainer(model, lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm)
     scheduler = PlateauScheduler(trainer, patience=5, factor=0.5)
     # the reference's kornia augmentations of each training sample (data.py:222-224), on the device
     trainer.augment = DeviceAugmentation(cfg.augmentation_config, train=True, seed=cfg.random_seed + 1000 * rank)
@@ -274,7 +295,7 @@ def train(cfg: TrainConfig, rank: int = 0) -> str:
         if cfg.resident_dataset:  # the loaders' own set_epoch: sample order and arcs of this epoch
             train_loader.set_epoch(epoch)
             val_loader.set_epoch(epoch)
-        model.train()
+        model.train(not cfg.freeze_bn)
         epoch_losses = []
         for example in train_loader:
             images = trainer.augment(example["images"].to(device, non_blocking=True))
@@ -373,6 +394,8 @@ def parse_args(argv=None) -> TrainConfig:
     ns = vars(ap.parse_args(argv))
     if ns.get("dataset_config.dataset_path") is None:
         ap.error("--dataset-config.dataset-path is required")
+    if ns.get("freeze_bn") and ns.get("multigpu"):
+        ap.error("--freeze-bn is single-process: frozen-BatchNorm fine-tuning is not data-parallel (drop --multigpu)")
     if ns.get("float32_matmul_precision") not in (None, "highest", "high"):
         ap.error("--float32-matmul-precision must be 'highest' or 'high'")
     return _build(TrainConfig, ns)

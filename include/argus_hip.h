@@ -202,6 +202,45 @@ int argus_conv_infer_dgrad_plan(const argus_conv_desc* d, int dtype, int splits_
 int argus_conv_infer_dgrad(const argus_conv_desc* d, int dtype, const void* dy, const void* w_fold_dgrad,
                            const void* addend, const void* mask_src, void* dx, int splits, void* workspace,
                            size_t workspace_bytes, argus_stream_t stream);
+/* ---- frozen fine-tuning (ABI 21, added without a version change: detect by symbol) --------------
+ * Parameter gradients of the folded network: what loss.backward() leaves in .grad through nn.Conv2d +
+ * nn.BatchNorm2d.eval() of torchvision's Bottleneck.forward with the model in eval mode (argus/models.py:66-90,
+ * argus/train.py:298-321 after model.eval()). From a conv's input x and the masked output gradient dm that
+ * argus_conv_infer_dgrad's chain produces, argus_conv_wgrad(x, dm) is dL/d(w_fold); the two entries below add
+ * dL/d(bias) and the chain rule through argus_conv_fold_bn back to (w, gamma, beta). Nothing here allocates or
+ * synchronises: every call can be captured into a graph. No floating-point atomics; plain vector stores.
+ *
+ * argus_bias_grad: db[k] (fp32) = sum_p dm[p][k] over an NHWC [pixels][channels] tensor in dtype ARGUS_F32 or
+ * ARGUS_BF16 (ARGUS_F16, ARGUS_FP8 and unknown values: ARGUS_ERR_ARG, "dtype" in the message); channels a
+ * multiple of 64, dm 16-byte aligned. The pixels may be sliced over workgroups: splits 0 = the library's
+ * choice, 1 = no split (no workspace touched, workspace may be NULL), up to *max_splits of the plan
+ * (min(pixels, 64)); each slice stores an fp64 partial row and the last-arriving workgroup of a 64-column
+ * block adds the slices in slice order, so the result is bitwise reproducible for a given `splits`. A thread
+ * adds runs of at most 64 rows in fp32, everything above in fp64, rounded once:
+ * |db[k] - exact| <= 64 * 2^-24 * sum_p |dm[p][k]|. Workspace (16-byte aligned): uint32 tickets in the first
+ * 4096 bytes, zero on entry and on return, the partial rows from byte 4096 on - argus_conv_infer_workspace_bytes'
+ * layout, so one zeroed-once workspace serves argus_conv_infer, argus_conv_infer_dgrad and this entry in
+ * stream order, and consecutive calls of different shapes.
+ * argus_bias_grad_plan: as argus_conv_infer_dgrad_plan: *splits = splits_in or the library's choice for
+ * splits_in == 0, *max_splits, *workspace_bytes = what *splits slices need (0 for <= 1). */
+int argus_bias_grad_plan(int dtype, int64_t pixels, int channels, int splits_in, int* splits, int* max_splits,
+                         size_t* workspace_bytes);
+int argus_bias_grad(int dtype, int64_t pixels, int channels, const void* dm, float* db, int splits, void* workspace,
+                    size_t workspace_bytes, argus_stream_t stream);
+/* The derivative of argus_conv_fold_bn (fp32 throughout; `d` as for the fold, w_master read through `strides`
+ * as the fold reads it, NULL = OHWI contiguous). With invstd = 1 / sqrt(running_var + eps) and scale = gamma *
+ * invstd, bit-identical to argus_bn_eval_coeffs, dwf [k][r*s*c] = dL/d(w_fold) as argus_conv_wgrad writes it and
+ * db = dL/d(bias):
+ *   dw[k][j] = scale[k] * dwf[k][j]       OHWI contiguous; dw == dwf (in place) is allowed
+ *   dgamma[k] = invstd[k] * (sum_j dwf[k][j] * w[k][j] - running_mean[k] * db[k])
+ *   dbeta[k] = db[k]                      dbeta == db is allowed
+ * The fold's rounding of w * scale to the compute dtype is treated as the identity (straight-through). The row
+ * sum is 64 lane-strided partials and a fixed 6-level tree (at most 72 + 6 additions deep), one launch per
+ * conv, one wave per filter row, no workspace. dwf and dw 16-byte aligned. */
+int argus_conv_fold_bn_bwd(const argus_conv_desc* d, const float* w_master, const int64_t* strides,
+                           const float* gamma, const float* running_mean, const float* running_var, float eps,
+                           const float* dwf, const float* db, float* dw, float* dgamma, float* dbeta,
+                           argus_stream_t stream);
 
 int argus_conv_fwd_stat_rows(const argus_conv_desc* d, int dtype);
 int argus_conv_fwd_stat_tile(const argus_conv_desc* d, int dtype);
