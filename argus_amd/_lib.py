@@ -85,6 +85,18 @@ class FrameSrc(C.Structure):
                 ("y0", C.c_int32), ("x0", C.c_int32)]
 
 
+class FoldSrc(C.Structure):
+    """argus_conv_fold_src (include/argus_hip.h): one conv of argus_conv_fold_bn_table."""
+
+    _fields_ = [("desc", ConvDesc), ("w_master", C.c_void_p), ("strides", C.POINTER(C.c_int64)),
+                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p),
+                ("running_var", C.c_void_p), ("eps", C.c_float), ("w_fold", C.c_void_p), ("bias", C.c_void_p),
+                ("w_fold_dgrad", C.c_void_p), ("dwf", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p),
+                ("dgamma", C.c_void_p), ("dbeta", C.c_void_p)]
+
+
+FOLD_ENTRY_BYTES = 176  # ARGUS_CONV_FOLD_ENTRY_BYTES
+
 _P = C.c_void_p
 _I = C.c_int
 _I64 = C.c_int64
@@ -116,6 +128,9 @@ SIGNATURES = {
     "argus_bias_grad_plan": (_I, [_I, _I64, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_SZ)]),
     "argus_bias_grad": (_I, [_I, _I64, _I, _P, _P, _I, _P, _SZ, _P]),
     "argus_conv_fold_bn_bwd": (_I, [_DESC, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P]),
+    "argus_conv_fold_bn_table": (_I, [_I, C.POINTER(FoldSrc), _P, _SZ, C.POINTER(_I), C.POINTER(_I)]),
+    "argus_conv_fold_bn_batch": (_I, [_I, _I, _P, _I, _P]),
+    "argus_conv_fold_bn_bwd_batch": (_I, [_I, _P, _I, _P]),
     "argus_conv_x8_ok": (_I, [_DESC, _I]),
     "argus_conv_fwd_stats_only_rows": (_I, [_DESC, _I]),
     "argus_conv_fwd_stats_only_tile": (_I, [_DESC, _I]),

@@ -151,6 +151,15 @@ int argus_conv_fold_bn(const argus_conv_desc* d, int dtype, const float* w_maste
                       (hipStream_t)stream);
 }
 
+int argus_conv_fold_bn_table(int count, const argus_conv_fold_src* src, void* host_table, size_t table_bytes,
+                             int* nblocks_fold, int* nblocks_bwd) {
+  return conv_fold_bn_table(count, src, host_table, table_bytes, nblocks_fold, nblocks_bwd);
+}
+
+int argus_conv_fold_bn_batch(int dtype, int count, const void* device_table, int nblocks, argus_stream_t stream) {
+  return conv_fold_bn_batch(dtype, count, device_table, nblocks, (hipStream_t)stream);
+}
+
 int argus_conv_infer_splits(const argus_conv_desc* d, int dtype) { return d ? conv_infer_splits(*d, dtype) : 0; }
 int argus_conv_infer_max_splits(const argus_conv_desc* d, int dtype) {
   return d ? conv_infer_max_splits(*d, dtype) : 0;

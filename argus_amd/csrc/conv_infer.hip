@@ -52,6 +52,83 @@ __global__ __launch_bounds__(256) void fold_bn_kernel(const float* __restrict__ 
   }
 }
 
+// ---- table-driven fold --------------------------------------------------------------------------------
+// Both layouts of every conv of a table in one launch (argus_conv_fold_bn_batch). A workgroup owns the 64(k) x
+// 64(c) tile of one tap of one entry, found by search over the entries' first workgroup as in
+// weight_prep_batch_kernel. Thread (row = tid / 4, cq = 16 * (tid % 4)) reads 16 consecutive channels of filter
+// k0 + row through the master's strides (16-byte loads when the channels are contiguous), forms v exactly as
+// fold_bn_kernel does and stores its piece of the forward row w_fold[k][r][s][c0 + cq ..]. The transposed copy
+// goes through the LDS: the same thread then holds 16 consecutive filters of channel c0 + row and stores its
+// piece of w_fold_dgrad[c][R-1-r][S-1-s][k0 + cq ..], so both copies leave in 16-byte stores, four lanes to a
+// 256-byte (fp32) / 128-byte (bf16) row segment; fold_bn_kernel<T, true> gathers this copy with a stride of a
+// whole filter row per element instead.
+// LDS layout: the tile holds fp32 values (already rounded to T, so both copies pack the same bits), element
+// (k, c) at k * 129 + 8 * (k / 16) + c + 8 * (c / 16). ds_write_b32 / ds_read_b32 bank 32-lane halves over 32
+// dwords; a half is 8 rows x 4 quarters. Writing column 16 q + j of rows k..k+7 lands on bank k + 24 q + const,
+// reading row 16 q + j at columns c..c+7 on bank c + 24 q + const (mod 32): {0, 24, 16, 8} + 0..7, all
+// distinct, so neither side conflicts (a plain pitch of 65 puts quarters 0 and 2 on the same banks).
+constexpr int kFoldPitch = 129;  // 1 mod 32, >= 64 + 2 * 24 columns of skew
+ARGUS_DEV int fold_lds(int k, int c) { return k * kFoldPitch + 8 * (k >> 4) + c + 8 * (c >> 4); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void fold_bn_kernel_batch(const FoldEntry* __restrict__ tab, int count) {
+  int lo = 0, hi = count - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) {  // last entry with blk0 <= b
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1;
+  }
+  const FoldEntry e = tab[lo];
+  const int local = b - e.blk0;
+  const int RS = e.R * e.S, ct = e.C / 64;
+  const int rs = local % RS, rem = local / RS;
+  const int c0 = (rem % ct) * 64, k0 = (rem / ct) * 64;
+  const int r = rs / e.S, s = rs - r * e.S;
+  __shared__ float tile[64 * kFoldPitch];
+  const int row = threadIdx.x >> 2, cq = (threadIdx.x & 3) * 16;
+  constexpr int E = Chunk<T>::E;
+  float sc, sh;
+  bn_eval_coeff(e.gamma, e.beta, e.rm, e.rv, e.eps, k0 + row, sc, sh);
+  const float* src = e.w + (long long)(k0 + row) * e.sk + r * e.sr + s * e.ss + (long long)(c0 + cq) * e.sc;
+  float f[16];
+  if (e.sc == 1 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+#pragma unroll
+    for (int j = 0; j < 16; j += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + j);
+      f[j] = v.x; f[j + 1] = v.y; f[j + 2] = v.z; f[j + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) f[j] = src[j * e.sc];
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) f[j] = to_f32(from_f32<T>(f[j] * sc));  // the one multiply and the one rounding
+  T* dst = reinterpret_cast<T*>(e.wf) + ((size_t)(k0 + row) * RS + rs) * e.C + c0 + cq;
+#pragma unroll
+  for (int j = 0; j < 16; j += E) {
+    float g[E];
+#pragma unroll
+    for (int u = 0; u < E; ++u) g[u] = f[j + u];
+    st16(dst + j, ChunkCvt<T>::pack(g));
+  }
+  if (rs == 0 && c0 == 0 && cq == 0) e.bias[k0 + row] = sh;  // once per filter
+  if (!e.wfd) return;  // (uniform: the whole entry has no second copy)
+#pragma unroll
+  for (int j = 0; j < 16; ++j) tile[fold_lds(row, cq + j)] = f[j];
+  __syncthreads();
+  float t[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) t[j] = tile[fold_lds(cq + j, row)];  // row = channel, 16 consecutive filters
+  T* dd = reinterpret_cast<T*>(e.wfd) + ((size_t)(c0 + row) * RS + (RS - 1 - rs)) * e.K + k0 + cq;
+#pragma unroll
+  for (int j = 0; j < 16; j += E) {
+    float g[E];
+#pragma unroll
+    for (int u = 0; u < E; ++u) g[u] = t[j + u];
+    st16(dd + j, ChunkCvt<T>::pack(g));
+  }
+}
+
 // ---- forward ------------------------------------------------------------------------------------------
 // a row = one output pixel (nimg, oh, ow); off: element offset of its window's (0, 0) tap before padding
 template <int AR>
@@ -212,6 +289,93 @@ int conv_fold_bn(const argus_conv_desc& d, int dtype, const float* w, const int6
 int conv_fold_bn_dgrad(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides, const float* gamma,
                        const float* beta, const float* rm, const float* rv, float eps, void* wfd, hipStream_t st) {
   return fold_bn<true>(d, dtype, "conv_fold_bn_dgrad", w, strides, gamma, beta, rm, rv, eps, wfd, nullptr, st);
+}
+
+int conv_fold_bn_table(int count, const argus_conv_fold_src* src, void* host_table, size_t bytes, int* nblocks_fold,
+                       int* nblocks_bwd) {
+  if (!src || !host_table || !nblocks_fold || !nblocks_bwd) {
+    set_error("conv_fold_bn_table: null argument");
+    return ARGUS_ERR_ARG;
+  }
+  if (count <= 0) { set_error("conv_fold_bn_table: count must be positive"); return ARGUS_ERR_ARG; }
+  const size_t need = (size_t)count * sizeof(FoldEntry);
+  if (bytes < need) {
+    set_error("conv_fold_bn_table: table of " + std::to_string(bytes) + " bytes, " + std::to_string(need) +
+              " needed for " + std::to_string(count) + " entries (ARGUS_CONV_FOLD_ENTRY_BYTES each)");
+    return ARGUS_ERR_ARG;
+  }
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  FoldEntry* tab = reinterpret_cast<FoldEntry*>(host_table);
+  long long blk = 0, row = 0;
+  int with_bwd = 0;
+  for (int i = 0; i < count; ++i) {
+    const argus_conv_fold_src& s = src[i];
+    const argus_conv_desc& d = s.desc;
+    const std::string who = "conv_fold_bn_table: entry " + std::to_string(i);
+    if (int e = infer_check(d, ARGUS_F32, who.c_str(), false)) return e;
+    if (!s.w_master || !s.gamma || !s.beta || !s.running_mean || !s.running_var || !s.w_fold || !s.bias) {
+      set_error(who + ": null argument");
+      return ARGUS_ERR_ARG;
+    }
+    const int nb = (s.dwf != nullptr) + (s.dw != nullptr) + (s.db != nullptr) + (s.dgamma != nullptr) +
+                   (s.dbeta != nullptr);
+    if (nb != 0 && nb != 5) {
+      set_error(who + ": null argument (dwf, dw, db, dgamma, dbeta: all five or none)");
+      return ARGUS_ERR_ARG;
+    }
+    with_bwd += nb == 5;
+    if (misaligned(s.w_fold) || misaligned(s.w_fold_dgrad)) {
+      set_error(who + ": w_fold and w_fold_dgrad must be 16-byte aligned");
+      return ARGUS_ERR_ARG;
+    }
+    if (misaligned(s.dwf) || misaligned(s.dw)) {
+      set_error(who + ": dwf and dw must be 16-byte aligned");
+      return ARGUS_ERR_ARG;
+    }
+    FoldEntry& t = tab[i];
+    t = FoldEntry{};
+    t.w = s.w_master;
+    if (s.strides) { t.sk = s.strides[0]; t.sc = s.strides[1]; t.sr = s.strides[2]; t.ss = s.strides[3]; }
+    else { t.sk = (long long)d.r * d.s * d.c; t.sc = 1; t.sr = (long long)d.s * d.c; t.ss = d.c; }  // OHWI contiguous
+    t.gamma = s.gamma; t.beta = s.beta; t.rm = s.running_mean; t.rv = s.running_var; t.eps = s.eps;
+    t.wf = s.w_fold; t.bias = s.bias; t.wfd = s.w_fold_dgrad;
+    t.dwf = s.dwf; t.dw = s.dw; t.db = s.db; t.dgamma = s.dgamma; t.dbeta = s.dbeta;
+    t.K = d.k; t.R = d.r; t.S = d.s; t.C = d.c;
+    t.blk0 = (int)blk; t.row0 = (int)row;
+    t.vec_w = fold_bwd_vec_w(d, t.w, t.sk, t.sc, t.sr, t.ss);
+    blk += (long long)(d.k / 64) * (d.c / 64) * d.r * d.s;
+    row += d.k / 4;
+    if (blk > INT32_MAX) { set_error("conv_fold_bn_table: more than 2^31 tiles"); return ARGUS_ERR_SHAPE; }
+  }
+  if (with_bwd != 0 && with_bwd != count) {
+    set_error("conv_fold_bn_table: null argument (the backward operands are given for every entry or for none)");
+    return ARGUS_ERR_ARG;
+  }
+  *nblocks_fold = (int)blk;
+  *nblocks_bwd = with_bwd ? (int)row : 0;
+  return ARGUS_OK;
+}
+
+int conv_fold_bn_batch(int dtype, int count, const void* device_table, int nblocks, hipStream_t st) {
+  if (dtype != ARGUS_F32 && dtype != ARGUS_BF16) {
+    set_error("conv_fold_bn_batch: dtype must be ARGUS_F32 or ARGUS_BF16 (ARGUS_F16 folds per conv: "
+              "argus_conv_fold_bn)");
+    return ARGUS_ERR_ARG;
+  }
+  if (!device_table) { set_error("conv_fold_bn_batch: null argument"); return ARGUS_ERR_ARG; }
+  if (count <= 0 || nblocks <= 0) {
+    set_error("conv_fold_bn_batch: count and nblocks must be positive (argus_conv_fold_bn_table)");
+    return ARGUS_ERR_ARG;
+  }
+  g_launch_work = g_launch_bytes = 0.0;  // (the shapes live in the device table)
+  const FoldEntry* tab = reinterpret_cast<const FoldEntry*>(device_table);
+  if (dtype == ARGUS_BF16)
+    timed_launch("argus::fold_bn_kernel_batch<__bf16>", fold_bn_kernel_batch<bf16>, dim3(nblocks), dim3(256), st, tab,
+                 count);
+  else
+    timed_launch("argus::fold_bn_kernel_batch<float>", fold_bn_kernel_batch<float>, dim3(nblocks), dim3(256), st, tab,
+                 count);
+  return check_launch("fold_bn_kernel_batch");
 }
 
 int conv_infer(const argus_conv_desc& d, int dtype, const void* x, const void* w, const float* bias, const void* res,

@@ -156,13 +156,13 @@ static int bias_grad_plan(int dtype, int64_t pixels, int channels, int splits_in
 struct FoldBwdStrides { long long sk, sc, sr, ss; };
 constexpr int kFoldBwdBatch = 4;
 
+// filter row k of one conv, by one wave: the body of both kernels below
 template <bool kVecW>
-__global__ __launch_bounds__(256) void fold_bn_bwd_kernel(const float* __restrict__ w, FoldBwdStrides st,
-                                                          const float* __restrict__ gamma,
-                                                          const float* __restrict__ rm, const float* __restrict__ rv,
-                                                          float eps, const float* dwf, const float* db, float* dw,
-                                                          float* dgamma, float* dbeta, int R, int S, int C) {
-  const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);  // (K % 64 == 0: whole waves)
+ARGUS_DEV void fold_bn_bwd_row(const float* __restrict__ w, FoldBwdStrides st, const float* __restrict__ gamma,
+                               const float* __restrict__ rm, const float* __restrict__ rv, float eps,
+                               const float* dwf, const float* db, float* dw, float* dgamma, float* dbeta, int R, int S,
+                               int C, int k) {
+  const int lane = threadIdx.x & 63;
   const float inv = 1.f / sqrtf(rv[k] + eps);
   const float sc = gamma[k] * inv;
   const int J = R * S * C, nch = J / 4;
@@ -201,6 +201,42 @@ __global__ __launch_bounds__(256) void fold_bn_bwd_kernel(const float* __restric
   }
 }
 
+template <bool kVecW>
+__global__ __launch_bounds__(256) void fold_bn_bwd_kernel(const float* __restrict__ w, FoldBwdStrides st,
+                                                          const float* __restrict__ gamma,
+                                                          const float* __restrict__ rm, const float* __restrict__ rv,
+                                                          float eps, const float* dwf, const float* db, float* dw,
+                                                          float* dgamma, float* dbeta, int R, int S, int C) {
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);  // (K % 64 == 0: whole waves)
+  fold_bn_bwd_row<kVecW>(w, st, gamma, rm, rv, eps, dwf, db, dw, dgamma, dbeta, R, S, C, k);
+}
+
+// argus_conv_fold_bn_bwd_batch: the same rows for every entry of a table in one launch. A workgroup (4 rows)
+// finds its entry by search over the entries' first workgroup (weight_prep_batch_kernel's search); vec_w is the
+// host's choice of fold_bn_bwd_kernel<true / false> for that master. An entry whose db is another entry's dbeta
+// slot (a downsample under conv3) reads a word its owner rewrites with the value it already holds.
+__global__ __launch_bounds__(256) void fold_bn_bwd_kernel_batch(const FoldEntry* __restrict__ tab, int count) {
+  int lo = 0, hi = count - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) {  // last entry with row0 <= b
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].row0 <= b) lo = mid; else hi = mid - 1;
+  }
+  const FoldEntry e = tab[lo];
+  const int k = (b - e.row0) * 4 + (threadIdx.x >> 6);
+  const FoldBwdStrides st{e.sk, e.sc, e.sr, e.ss};
+  if (e.vec_w)
+    fold_bn_bwd_row<true>(e.w, st, e.gamma, e.rm, e.rv, e.eps, e.dwf, e.db, e.dw, e.dgamma, e.dbeta, e.R, e.S, e.C, k);
+  else
+    fold_bn_bwd_row<false>(e.w, st, e.gamma, e.rm, e.rv, e.eps, e.dwf, e.db, e.dw, e.dgamma, e.dbeta, e.R, e.S, e.C,
+                           k);
+}
+
+bool fold_bwd_vec_w(const argus_conv_desc& d, const float* w, long long sk, long long sc, long long sr,
+                    long long ss) {
+  return sc == 1 && ss == d.c && sr == (long long)d.s * d.c && sk % 4 == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+}
+
 static int fold_bn_bwd(const argus_conv_desc& d, const float* w, const int64_t* strides, const float* gamma,
                        const float* rm, const float* rv, float eps, const float* dwf, const float* db, float* dw,
                        float* dgamma, float* dbeta, hipStream_t st) {
@@ -208,8 +244,7 @@ static int fold_bn_bwd(const argus_conv_desc& d, const float* w, const int64_t* 
   FoldBwdStrides fs;
   if (strides) fs = {strides[0], strides[1], strides[2], strides[3]};
   else fs = {(long long)d.r * d.s * d.c, 1, (long long)d.s * d.c, d.c};  // OHWI contiguous
-  const bool vec = fs.sc == 1 && fs.ss == d.c && fs.sr == (long long)d.s * d.c && fs.sk % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+  const bool vec = fold_bwd_vec_w(d, w, fs.sk, fs.sc, fs.sr, fs.ss);
   if ((reinterpret_cast<uintptr_t>(dwf) | reinterpret_cast<uintptr_t>(dw)) & 15) {
     set_error("conv_fold_bn_bwd: dwf and dw must be 16-byte aligned");
     return ARGUS_ERR_ARG;
@@ -225,6 +260,19 @@ static int fold_bn_bwd(const argus_conv_desc& d, const float* w, const int64_t* 
     timed_launch("argus::fold_bn_bwd_kernel<false>", fold_bn_bwd_kernel<false>, grid, dim3(256), st, w, fs, gamma, rm,
                  rv, eps, dwf, db, dw, dgamma, dbeta, d.r, d.s, d.c);
   return check_launch("fold_bn_bwd_kernel");
+}
+
+int conv_fold_bn_bwd_batch(int count, const void* device_table, int nblocks, hipStream_t st) {
+  if (!device_table) { set_error("conv_fold_bn_bwd_batch: null argument"); return ARGUS_ERR_ARG; }
+  if (count <= 0 || nblocks <= 0) {
+    set_error("conv_fold_bn_bwd_batch: count and nblocks must be positive (argus_conv_fold_bn_table; a table "
+              "without the backward operands has no backward grid)");
+    return ARGUS_ERR_ARG;
+  }
+  g_launch_work = g_launch_bytes = 0.0;  // (the shapes live in the device table)
+  timed_launch("argus::fold_bn_bwd_kernel_batch", fold_bn_bwd_kernel_batch, dim3(nblocks), dim3(256), st,
+               reinterpret_cast<const FoldEntry*>(device_table), count);
+  return check_launch("fold_bn_bwd_kernel_batch");
 }
 
 }  // namespace argus
@@ -281,4 +329,8 @@ extern "C" int argus_conv_fold_bn_bwd(const argus_conv_desc* d, const float* w_m
   }
   return fold_bn_bwd(*d, w_master, strides, gamma, running_mean, running_var, eps, dwf, db, dw, dgamma, dbeta,
                      (hipStream_t)stream);
+}
+
+extern "C" int argus_conv_fold_bn_bwd_batch(int count, const void* device_table, int nblocks, argus_stream_t stream) {
+  return conv_fold_bn_bwd_batch(count, device_table, nblocks, (hipStream_t)stream);
 }

@@ -118,6 +118,30 @@ int conv_fold_bn(const argus_conv_desc& d, int dtype, const float* w, const int6
                  hipStream_t st);
 int conv_fold_bn_dgrad(const argus_conv_desc& d, int dtype, const float* w, const int64_t* strides, const float* gamma,
                        const float* beta, const float* rm, const float* rv, float eps, void* wfd, hipStream_t st);
+// One entry of the table behind argus_conv_fold_bn_batch (conv_infer.hip) and argus_conv_fold_bn_bwd_batch
+// (conv_infer_wgrad.hip): a conv's fold and its derivative, every pointer a device pointer. blk0 / row0: the first
+// workgroup of this entry in the fold grid (64 x 64 tiles per tap) and in the backward grid (4 filter rows each).
+struct FoldEntry {
+  const float* w;
+  long long sk, sc, sr, ss;
+  const float *gamma, *beta, *rm, *rv;
+  void* wf;
+  float* bias;
+  void* wfd;
+  const float* dwf;
+  float* dw;
+  const float* db;
+  float *dgamma, *dbeta;
+  float eps;
+  int K, R, S, C, blk0, row0, vec_w, pad[2];
+};
+static_assert(sizeof(FoldEntry) == ARGUS_CONV_FOLD_ENTRY_BYTES, "argus_hip.h: ARGUS_CONV_FOLD_ENTRY_BYTES");
+int conv_fold_bn_table(int count, const argus_conv_fold_src* src, void* host_table, size_t bytes, int* nblocks_fold,
+                       int* nblocks_bwd);
+int conv_fold_bn_batch(int dtype, int count, const void* device_table, int nblocks, hipStream_t st);
+int conv_fold_bn_bwd_batch(int count, const void* device_table, int nblocks, hipStream_t st);
+// whether argus_conv_fold_bn_bwd reads this master with 16-byte loads (the row is OHWI-contiguous in memory)
+bool fold_bwd_vec_w(const argus_conv_desc& d, const float* w, long long sk, long long sc, long long sr, long long ss);
 int conv_infer_splits(const argus_conv_desc& d, int dtype);
 int conv_infer_max_splits(const argus_conv_desc& d, int dtype);
 size_t conv_infer_ws_bytes(const argus_conv_desc& d, int dtype, int splits);

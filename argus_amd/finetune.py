@@ -11,10 +11,11 @@ A ``FineTuneSession`` is a ``GradientSession`` that adds the parameter gradients
 - the parameters live in a ``step.FlatParams`` (the model's parameters become views of it, as under
   ``FusedTrainer``; one they are already views of is taken over), the folds read those masters, the head reads them
   directly;
-- ``step()`` re-folds both weight copies from the masters, runs the frozen forward, ``argus_se3_loss`` and the
-  ``GradientSession`` backward; while a block's operands are alive, each conv's ``argus_conv_wgrad`` writes
-  dL/d(w_fold) straight into the flat gradient slot, ``argus_bias_grad`` sums dm into dL/d(bias) and
-  ``argus_conv_fold_bn_bwd`` applies the chain rule through the fold in place, giving the gradients of
+- ``step()`` re-folds both weight copies of the trainable convs from the masters (one table-driven launch,
+  ``argus_conv_fold_bn_batch``), runs the frozen forward, ``argus_se3_loss`` and the ``GradientSession`` backward;
+  while a block's operands are alive, each conv's ``argus_conv_wgrad`` writes dL/d(w_fold) straight into the flat
+  gradient slot and ``argus_bias_grad`` sums dm into dL/d(bias); after the block loop one
+  ``argus_conv_fold_bn_bwd_batch`` applies the chain rule through every fold in place, giving the gradients of
   (w, gamma, beta). The stem, which is not folded, uses the training entries (``argus_maxpool_bwd_bn`` with the
   running mean and invstd, ``argus_bn_bwd_finalize``, ``argus_conv_wgrad_apply``); the head is
   ``ResNetEngine.backward``'s ``head_wgrads``. ``argus_global_norm`` closes the graph: a linear chain on one
@@ -22,6 +23,12 @@ A ``FineTuneSession`` is a ``GradientSession`` that adds the parameter gradients
 - ``argus_adam_step`` (clip + Adam, lr and bias corrections by value) is launched after the replay, then a
   second small graph re-folds, so ``session(images)``, ``pose``, ``vjp`` and ``image_gradient`` see the
   updated parameters.
+
+``trainable="layerK"`` trains ``resnet.layerK`` .. ``resnet.layer4``, ``resnet.fc`` and ``output_mlp`` (stock PyTorch:
+``requires_grad_(False)`` on everything before, ``model.eval()``, ``clip_grad_norm_`` and ``Adam`` over the rest). The
+flat buffer is in model order, so that is a suffix of it, as the head is: norm and Adam run over the suffix, the
+backward's block loop stops at ``layerK.0`` (whose conv1 and downsample get no data gradient: nobody reads it), and
+nothing of the stem's backward is launched. The forward and everything the session serves stay at full depth.
 
 The session writes parameters only through Adam: never a BN buffer, never ``num_batches_tracked``, and it
 never calls ``model.train()``. fp32 and bf16, one process (no data-parallel fine-tuning).
@@ -34,12 +41,13 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from argus_amd._lib import BnBwdPrologue, ptr, stream
+from argus_amd._lib import FOLD_ENTRY_BYTES, BnBwdPrologue, FoldSrc, ptr, stream
 from argus_amd.infer_grad import SERVED, GradientSession
 from argus_amd.models import NCameraCNN
 from argus_amd.step import FlatParams
 
-TRAINABLE = ("all", "head")
+STAGES = ("layer1", "layer2", "layer3", "layer4")
+TRAINABLE = ("all", "head") + STAGES
 HEAD = ("resnet.fc", "output_mlp.0", "output_mlp.2", "output_mlp.4")
 
 
@@ -107,9 +115,13 @@ class FineTuneSession(GradientSession):
     ``GradientSession`` serves, at the current parameters.
 
     ``trainable="head"`` trains ``resnet.fc`` and ``output_mlp`` only: no conv data gradient, weight gradient or
-    fold is launched, the backbone gradients stay zero and its parameters bit-identical. ``debug=True`` runs
-    eagerly and adds ``wgrad.<conv>`` (dL/d w_fold), ``dbias.<conv>`` and ``fold_bwd.<conv>`` (a tuple
-    dw, dgamma, dbeta) to ``session.debug``, beside ``stem.*`` and ``head.*``. ``lr`` is writable."""
+    fold is launched, the backbone gradients stay zero and its parameters bit-identical. ``trainable="layerK"``
+    (K = 1..4) trains ``resnet.layerK`` and everything behind it; the stem and the earlier stages are frozen: their
+    parameters, gradient slots and Adam moments are never written. A step re-folds what its own session trains:
+    after a session that trains more has stepped on the same model, ``refresh()`` this one first. ``launch_plan``
+    counts the launches of a step by kind. ``debug=True`` runs eagerly and adds ``wgrad.<conv>`` (dL/d w_fold),
+    ``dbias.<conv>`` and ``fold_bwd.<conv>`` (a tuple dw, dgamma, dbeta) to ``session.debug``, beside ``stem.*`` and
+    ``head.*``, for what was launched. ``lr`` is writable."""
 
     def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
                  lr: float = 1e-4, max_grad_norm: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -119,7 +131,8 @@ class FineTuneSession(GradientSession):
             raise ValueError(f"FineTuneSession serves compute_dtype 'fp32' and 'bf16', got {dtype!r} (no fp16, fp8 "
                              f"or bf16x3 fine-tuning)")
         if trainable not in TRAINABLE:
-            raise ValueError(f"FineTuneSession: trainable must be 'all' or 'head', got {trainable!r}")
+            raise ValueError(f"FineTuneSession: trainable must be one of {', '.join(map(repr, TRAINABLE))}, got "
+                             f"{trainable!r}")
         if next(model.parameters()).device.type != "cuda":
             raise RuntimeError("argus_amd.FineTuneSession runs only on the MI355X HIP path: move the model to a "
                                "cuda device (there is no CPU fallback)")
@@ -142,17 +155,36 @@ class FineTuneSession(GradientSession):
         h0 = names.index("resnet.fc.weight")
         if any(not n.startswith(HEAD) for n in names[h0:]) or any(n.startswith(HEAD) for n in names[:h0]):
             raise RuntimeError("FineTuneSession: the head parameters must be the last slots of the flat buffer")
-        # what Adam steps over: everything, or the head's suffix of the flat buffer
-        self.opt_begin = 0 if self.trainable == "all" else self.flat.offset["resnet.fc.weight"]
+        # what Adam steps over: everything, or a suffix of the flat buffer (model order: a stage's first
+        # parameter follows the last one of the stage before it, the head follows layer4)
+        first = {"all": names[0], "head": "resnet.fc.weight"}.get(self.trainable,
+                                                                  f"resnet.{self.trainable}.0.conv1.weight")
+        self.opt_begin = self.flat.offset[first]
         self.opt_count = self.flat.total - self.opt_begin
+        # the blocks the backward visits: schedule[first_block:], none for "head"; the stem only under "all"
+        self.first_block = len(self.schedule)
+        if self.trainable != "head":
+            self.first_block = next(i for i, (c1, *_) in enumerate(self.schedule) if c1.name + ".weight" == first) \
+                if self.trainable in STAGES else 0
+        self.train_convs = [cv for blk in self.schedule[self.first_block:] for cv in blk if cv is not None]
+        trained = {cv.name for cv in self.train_convs} | {cv.bn for cv in self.train_convs}
+        i0 = names.index(first)
+        if self.trainable in STAGES and (
+                any(n.rsplit(".", 1)[0] not in trained and not n.startswith(HEAD) for n in names[i0:]) or
+                any(n.rsplit(".", 1)[0] in trained for n in names[:i0])):
+            raise RuntimeError(f"FineTuneSession: {self.trainable} and everything behind it must be the last slots "
+                               f"of the flat buffer")
         self.norm = self._empty(1, dtype=torch.float32)
         self.norm_ws = self._empty(max(L.dll.argus_sumsq_workspace_bytes(self.opt_count), 16), dtype=torch.uint8)
         hws = max(L.dll.argus_gemm_f32_workspace_bytes(*s) for s in
                   [(6, 128, B), (128, 128, B), (128, D, B), (R, 2048, N)])
         if hws > self.gemm_ws.numel():
             self.gemm_ws = self._empty(hws, dtype=torch.uint8)
-        self.launches_per_step = self.launches_per_forward + 1 + 3 + 8 + 1 + 1  # loss, head chain, head grads, norm, Adam
+        # by kind; their sum is launches_per_step. head: the three GELU-backward GEMMs and the eight gradients
+        self.launch_plan = {"forward": self.launches_per_forward, "loss": 1, "head": 3 + 8, "norm": 1, "adam": 1}
+        self.launches_per_step = sum(self.launch_plan.values())
         self.launches_per_refold = 0
+        self._fold_n = 0
         if self.trainable == "head":
             return
         ws_bytes, wg_bytes = self.ws.numel(), L.dll.argus_conv_wgrad_workspace_bytes(C.byref(self.stem_desc), dt)
@@ -172,12 +204,21 @@ class FineTuneSession(GradientSession):
         self.stem_invstd = self._empty(64, dtype=torch.float32)
         self.bn_ws = torch.zeros(L.dll.argus_bn_workspace_bytes(64), dtype=torch.uint8, device=self.device)
         self.stem_cabc = self._empty(3, 64, dtype=torch.float32)
-        n_ds = sum(1 for *_, ds in self.schedule if ds is not None)
-        self.launches_per_refold = 2 + 2 * len(self.convs)
-        # + the backbone's data gradients, per conv wgrad (+ its split reduce) / fold_bwd, a bias sum per dm,
-        # the stem's three
-        self.launches_per_step += (self.launches_per_refold + (self.launches_per_backward - 4) +
-                                   3 * len(self.convs) + (len(self.convs) - n_ds) + 3)
+        all_, n = self.trainable == "all", len(self.train_convs)
+        n_ds = sum(1 for *_, ds in self.schedule[self.first_block:] if ds is not None)
+        # the device table of argus_conv_fold_bn_batch / _bwd_batch over the trainable convs (filled by refresh)
+        self._fold_n = n
+        self._fold_table = torch.zeros(n * FOLD_ENTRY_BYTES, dtype=torch.uint8, device=self.device)
+        # the stem copy and its BN coefficients (under "all"), one batched fold
+        self.launches_per_refold = (2 if all_ else 0) + 1
+        # the boundary block of a stage suffix launches no data gradient for conv1 and the downsample
+        boundary = 0 if all_ else 1 + (self.schedule[self.first_block][3] is not None)
+        self.launch_plan.update({
+            "refold": self.launches_per_refold, "fc_dgrad": 1, "avgpool_bwd": 1, "dgrad": n - boundary,
+            "wgrad": 2 * n,  # (+ its split reduce)
+            "bias_grad": n - n_ds, "fold_bwd": n if self.debug is not None else 1,
+            "stem": 4 if all_ else 0})  # max-pool backward, BN finalize, weight gradient (+ its reduce)
+        self.launches_per_step = sum(self.launch_plan.values())
 
     def refresh(self) -> None:
         """Re-fold both weight copies from the masters; the head reads the masters themselves."""
@@ -202,14 +243,36 @@ class FineTuneSession(GradientSession):
         if self.trainable == "all":
             with torch.no_grad():
                 torch.rsqrt(Bf["resnet.bn1.running_var"] + eps["resnet.bn1"], out=self.stem_invstd)
+        if self._fold_n:
+            self._fill_fold_table()
+
+    def _fill_fold_table(self) -> None:
+        """The table of both batched fold entries from the recorded master pointers, into the device tensor the
+        captured graphs read (its address never changes; the pointers in it only when the model was re-homed)."""
+        G, n = self.flat.G, self._fold_n
+        src = (FoldSrc * n)()
+        ds_of = {ds.name: c3 for _, _, c3, ds in self.schedule if ds is not None}
+        for e, cv in zip(src, self.train_convs):
+            w, st, gamma, beta, rm, rv, eps = self._masters[cv.name]
+            gw, gg, gb = G[cv.name + ".weight"], G[cv.bn + ".weight"], G[cv.bn + ".bias"]
+            db = G[ds_of[cv.name].bn + ".bias"] if cv.name in ds_of else gb  # the downsample shares conv3's bias sum
+            e.desc, e.w_master, e.strides = cv.desc, w, C.cast(st, C.POINTER(C.c_int64))
+            e.gamma, e.beta, e.running_mean, e.running_var, e.eps = gamma, beta, rm, rv, eps.value
+            e.w_fold, e.bias, e.w_fold_dgrad = ptr(cv.wf), ptr(cv.bias), ptr(cv.wfd)
+            e.dwf, e.dw, e.db, e.dgamma, e.dbeta = ptr(gw), ptr(gw), ptr(db), ptr(gg), ptr(gb)
+        host = torch.zeros(n * FOLD_ENTRY_BYTES, dtype=torch.uint8)
+        nf, nb = C.c_int(0), C.c_int(0)
+        self.L.conv_fold_bn_table(n, src, host.data_ptr(), host.numel(), C.byref(nf), C.byref(nb))
+        self._fold_blocks, self._fold_bwd_blocks = nf.value, nb.value
+        self._fold_table.copy_(host)
 
     def _refold(self) -> None:
         """refresh()'s launches from the recorded master pointers: capturable, nothing else."""
         L, dt, s = self.L, self.dt, stream()
-        L.conv_weight_prep(C.byref(self.stem_desc), dt, *self._stem_master, ptr(self.stem_wf), None, s)
-        L.bn_eval_coeffs(64, *self._bn1, ptr(self.stem_coef[0]), ptr(self.stem_coef[1]), s)
-        for cv in self.convs.values():
-            self._fold(cv, self._masters[cv.name], s)
+        if self.trainable == "all":
+            L.conv_weight_prep(C.byref(self.stem_desc), dt, *self._stem_master, ptr(self.stem_wf), None, s)
+            L.bn_eval_coeffs(64, *self._bn1, ptr(self.stem_coef[0]), ptr(self.stem_coef[1]), s)
+        L.conv_fold_bn_batch(dt, self._fold_n, ptr(self._fold_table), self._fold_blocks, s)
 
     # ------------------------------------------------------------------ parameter gradients
     def _head_grads(self, dpred: torch.Tensor) -> None:
@@ -235,9 +298,11 @@ class FineTuneSession(GradientSession):
                     self._keep(f"head.grad.{n}.{k}", G[f"{n}.{k}"])
 
     def _conv_grads(self, cv, x, dm, s, db_from=None) -> None:
-        """Gradients of (w, gamma, beta) of the folded conv ``cv`` from its input ``x`` and masked output gradient
-        ``dm``, into the flat slots. ``db_from``: the BN whose beta slot already holds sum(dm) (the downsample
-        shares conv3's dm)."""
+        """dL/d(w_fold) and dL/d(bias) of the folded conv ``cv`` from its input ``x`` and masked output gradient
+        ``dm``, into the flat slots of (w, beta). ``db_from``: the BN whose beta slot already holds sum(dm) (the
+        downsample shares conv3's dm). The fold's derivative then turns them into the gradients of (w, gamma,
+        beta) in place: one batched launch for all convs after the block loop, or here, per conv, under
+        ``debug`` (which keeps dL/d(w_fold) before it and the three gradients after it)."""
         L, dt, d, G = self.L, self.dt, cv.desc, self.flat.G
         gw, gg, gb = G[cv.name + ".weight"], G[cv.bn + ".weight"], G[cv.bn + ".bias"]
         L.conv_wgrad(C.byref(d), dt, ptr(x), None, None, ptr(dm), ptr(gw), ptr(self.wg_ws), self.wg_ws.numel(), s)
@@ -248,10 +313,11 @@ class FineTuneSession(GradientSession):
         else:
             db = G[db_from + ".bias"]
         self._keep("dbias." + cv.name, db)
+        if self.debug is None:
+            return
         w, st, gamma, _, rm, rv, eps = self._masters[cv.name]
         L.conv_fold_bn_bwd(C.byref(d), w, st, gamma, rm, rv, eps, ptr(gw), ptr(db), ptr(gw), ptr(gg), ptr(gb), s)
-        if self.debug is not None:
-            self.debug["fold_bwd." + cv.name] = (gw.clone(), gg.clone(), gb.clone())
+        self.debug["fold_bwd." + cv.name] = (gw.clone(), gg.clone(), gb.clone())
 
     def _backward_params(self, dpred: torch.Tensor) -> None:
         """GradientSession._backward's launches with every parameter gradient issued while its operands are alive
@@ -278,18 +344,20 @@ class FineTuneSession(GradientSession):
         last = self.acts[-1][2]
         L.avgpool_bwd_relu(dt, N, hf * wf, 2048, ptr(self.dfeat), ptr(last), ptr(dm3), s)
         self._keep("bwd.avgpool", dm3, last.shape)
-        for i in range(len(self.schedule) - 1, -1, -1):
+        all_ = self.trainable == "all"
+        for i in range(len(self.schedule) - 1, self.first_block - 1, -1):
             c1, c2, c3, ds = self.schedule[i]
             a1, a2, _ = self.acts[i]
             h = self.acts[i - 1][2] if i else self.p0
             pf = c1.name[:-len(".conv1")]
             self._dgrad(c3, dm3, None, a2, dm2, s, f"bwd.{pf}.conv3")
             self._dgrad(c2, dm2, None, a1, dm1, s, f"bwd.{pf}.conv2")
-            addend = dm3
-            if ds is not None:
-                self._dgrad(ds, dm3, None, None, dd, s, f"bwd.{pf}.downsample")
-                addend = dd
-            self._dgrad(c1, dm1, addend, h, dx, s, f"bwd.{pf}.conv1")
+            if all_ or i > self.first_block:  # (nobody reads the block input's gradient below a stage suffix)
+                addend = dm3
+                if ds is not None:
+                    self._dgrad(ds, dm3, None, None, dd, s, f"bwd.{pf}.downsample")
+                    addend = dd
+                self._dgrad(c1, dm1, addend, h, dx, s, f"bwd.{pf}.conv1")
             # dm3, dm2, dm1 and the saved a2, a1, h are all alive until the rotation below
             self._conv_grads(c3, a2, dm3, s)
             self._conv_grads(c2, a1, dm2, s)
@@ -297,6 +365,10 @@ class FineTuneSession(GradientSession):
             if ds is not None:
                 self._conv_grads(ds, h, dm3, s, db_from=c3.bn)
             dm3, dx = dx, dm3
+        if self.debug is None:  # the fold's derivative of every trainable conv, in place in the flat slots
+            L.conv_fold_bn_bwd_batch(self._fold_n, ptr(self._fold_table), self._fold_bwd_blocks, s)
+        if not all_:
+            return
         # stem: the max-pool backward through bn1's ReLU with the running mean / invstd, so that its partials are
         # {sum dm0, sum dm0 * xhat} = (dbeta, dgamma) of the eval-mode BN; then conv1's gradient of scale * dm0
         H1, W1 = self.stem_hw
@@ -350,10 +422,10 @@ class FineTuneSession(GradientSession):
             raise RuntimeError("FineTuneSession: the model's parameters were re-homed after this session was built")
         self.target.copy_(target)
         L, flat, st = self.L, self.flat, self.state
-        all_ = self.trainable == "all"
+        folds = self.trainable != "head"
 
         def body(x):
-            if all_:
+            if folds:
                 self._refold()
             self._forward(x)
             L.se3_loss(self.batch, ptr(self.pred), ptr(self.target), ptr(self.loss), ptr(self.dpred),
@@ -371,7 +443,7 @@ class FineTuneSession(GradientSession):
                         ptr(st.exp_avg_sq) + o, ptr(self.norm), C.c_float(1.0), C.c_float(self.max_grad_norm),
                         C.c_float(self.lr), C.c_float(b1), C.c_float(b2), C.c_float(self.eps),
                         C.c_float(self.weight_decay), C.c_float(1 - b1**t), C.c_float(1 - b2**t), stream())
-        if all_:  # the head reads the masters; the folded copies follow them
+        if folds:  # the head reads the masters; the folded copies follow them
             self._replay("refold", self._refold)
         return self.loss.clone()
 

@@ -100,9 +100,18 @@ class TrainConfig:
     # extension (--freeze-bn): fine-tune the eval-mode function (argus_amd.finetune.FineTuneSession): the model
     # stays in eval mode, BatchNorm uses and keeps its running statistics, only the parameters move
     freeze_bn: bool = False
+    # extension (--trainable {all,head,layer1..layer4}, with --freeze-bn): what the fine-tuning moves: everything,
+    # the head alone, or resnet.layerK and everything behind it (the stem and the earlier stages stay frozen)
+    trainable: str = "all"
 
     def __post_init__(self) -> None:
         assert isinstance(self.save_dir, str)
+        from argus_amd.finetune import TRAINABLE
+
+        if self.trainable not in TRAINABLE:
+            raise ValueError(f"trainable must be one of {', '.join(TRAINABLE)}, got {self.trainable!r}")
+        if self.trainable != "all" and not self.freeze_bn:
+            raise ValueError("--trainable needs --freeze-bn: the train-mode step trains every parameter")
         if self.freeze_bn and self.multigpu:
             raise ValueError("--freeze-bn is single-process: frozen-BatchNorm fine-tuning is not data-parallel "
                              "(drop --multigpu)")
@@ -257,7 +266,8 @@ def initialize_training(cfg: TrainConfig, rank: int = 0, world: int = 1):
     if cfg.freeze_bn:  # one FineTuneSession per batch size met, behind FusedTrainer's step / lr
         from argus_amd.finetune import FrozenTrainer
 
-        trainer = FrozenTrainer(model.eval(), lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm)
+        trainer = FrozenTrainer(model.eval(), lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm,
+                                trainable=cfg.trainable)
     else:
         trainer = FusedTrainer(model, lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm)
     scheduler = PlateauScheduler(trainer, patience=5, factor=0.5)
@@ -398,6 +408,12 @@ def parse_args(argv=None) -> TrainConfig:
         ap.error("--freeze-bn is single-process: frozen-BatchNorm fine-tuning is not data-parallel (drop --multigpu)")
     if ns.get("float32_matmul_precision") not in (None, "highest", "high"):
         ap.error("--float32-matmul-precision must be 'highest' or 'high'")
+    from argus_amd.finetune import TRAINABLE
+
+    if ns.get("trainable") is not None and ns["trainable"] not in TRAINABLE:
+        ap.error(f"--trainable must be one of {', '.join(TRAINABLE)}")
+    if ns.get("trainable") not in (None, "all") and not ns.get("freeze_bn"):
+        ap.error("--trainable needs --freeze-bn: the train-mode step trains every parameter")
     return _build(TrainConfig, ns)
 
 

@@ -241,6 +241,51 @@ int argus_conv_fold_bn_bwd(const argus_conv_desc* d, const float* w_master, cons
                            const float* gamma, const float* running_mean, const float* running_var, float eps,
                            const float* dwf, const float* db, float* dw, float* dgamma, float* dbeta,
                            argus_stream_t stream);
+/* Table-driven folds (ABI 21, added without a version change: detect by symbol): one launch for the folds of
+ * many convs and one for their derivatives, as argus_conv_weight_prep_batch is for argus_conv_weight_prep. A
+ * fine-tuning step re-folds every trainable conv twice per step and differentiates every fold once; at two to
+ * sixteen images these launches are short and their count is the cost.
+ *
+ * argus_conv_fold_bn_table writes `count` table entries of ARGUS_CONV_FOLD_ENTRY_BYTES each into host_table
+ * (table_bytes >= count * ARGUS_CONV_FOLD_ENTRY_BYTES) from `src`, one argus_conv_fold_src per conv:
+ *   desc                       the conv, of the kinds argus_conv_fold_bn serves (not the stem)
+ *   w_master, strides          as argus_conv_fold_bn (strides: 4 host int64, NULL = OHWI contiguous)
+ *   gamma, beta, running_mean, running_var, eps
+ *   w_fold, bias               argus_conv_fold_bn's outputs
+ *   w_fold_dgrad               argus_conv_fold_bn_dgrad's output, or NULL: that copy is not written
+ *   dwf, dw, db, dgamma, dbeta argus_conv_fold_bn_bwd's operands (dw may be dwf; db may be another entry's
+ *                              dbeta, which that entry's own db feeds: a downsample shares conv3's bias sum).
+ *                              All five NULL in every entry: a table for the fold alone (*nblocks_bwd = 0).
+ * and returns the two grid sizes. The caller copies host_table to device memory once; the table holds raw
+ * device pointers and the shapes, so it is rebuilt only when one of them changes. The launching entries cannot
+ * check a device table: pass the count and the grid sizes the table call returned.
+ *
+ * argus_conv_fold_bn_batch(dtype ARGUS_F32 or ARGUS_BF16; ARGUS_F16 stays on argus_conv_fold_bn): one launch
+ * that writes w_fold, bias and (where given) w_fold_dgrad of every entry, each bit-identical to
+ * argus_conv_fold_bn / argus_conv_fold_bn_dgrad. A workgroup owns a 64(k) x 64(c) tile of one filter tap: it
+ * reads the master tile once, forms T(w * scale[k]), stores the forward rows directly and the transposed,
+ * rotated rows through the LDS, both with 16-byte stores.
+ * argus_conv_fold_bn_bwd_batch: one launch, one wave per filter row of every entry, argus_conv_fold_bn_bwd's
+ * arithmetic in its order: bit-identical to it, in place or not. */
+#define ARGUS_CONV_FOLD_ENTRY_BYTES 176
+typedef struct {
+  argus_conv_desc desc;
+  const float* w_master;
+  const int64_t* strides;
+  const float *gamma, *beta, *running_mean, *running_var;
+  float eps;
+  void* w_fold;
+  float* bias;
+  void* w_fold_dgrad;
+  const float* dwf;
+  float* dw;
+  const float* db;
+  float *dgamma, *dbeta;
+} argus_conv_fold_src;
+int argus_conv_fold_bn_table(int count, const argus_conv_fold_src* src, void* host_table, size_t table_bytes,
+                             int* nblocks_fold, int* nblocks_bwd);
+int argus_conv_fold_bn_batch(int dtype, int count, const void* device_table, int nblocks, argus_stream_t stream);
+int argus_conv_fold_bn_bwd_batch(int count, const void* device_table, int nblocks, argus_stream_t stream);
 
 int argus_conv_fwd_stat_rows(const argus_conv_desc* d, int dtype);
 int argus_conv_fwd_stat_tile(const argus_conv_desc* d, int dtype);

@@ -11,7 +11,8 @@ min / mean per arm and round:
   b eager    the same launches issued eagerly (graph=False)
   c stock    what the reference does for such a step: the oracle's torch.nn model on the device in eval(), stock
              autograd (fp32; bf16 = torch.autocast(bfloat16)), clip_grad_norm_ and torch.optim.Adam over the trained
-             parameters (trainable "head": the backbone's requires_grad is off, so autograd stops at the head)
+             parameters (trainable "head" / "layerK": requires_grad is off on the frozen prefix, so autograd stops
+             at the head / at the stage boundary)
 
 Every arm trains its own copy of the weights; the step does not depend on their values. There is no pass/fail on
 time. The launches per step() are the session's own count of the entry points it issues (a split weight gradient or
@@ -49,14 +50,14 @@ def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dtype", choices=["fp32", "bf16"], default="bf16")
     ap.add_argument("--batch", type=int, default=2)
-    ap.add_argument("--trainable", choices=["all", "head"], default="all")
+    ap.add_argument("--trainable", choices=["all", "head", "layer1", "layer2", "layer3", "layer4"], default="all")
     ap.add_argument("--hw", type=int, nargs=2, default=[256, 256])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trials", type=int, default=50)
     ap.add_argument("--kernels", action="store_true")
     a = ap.parse_args(argv)
 
-    from argus_amd.finetune import HEAD, FineTuneSession
+    from argus_amd.finetune import FineTuneSession
     from argus_amd.losses import geometric_loss_fn
     from argus_amd.models import NCameraCNN
     from argus_amd.utils import se3_exp
@@ -92,8 +93,8 @@ def main(argv=None) -> None:
         rows = sorted(t.summary().items(), key=lambda kv: -kv[1]["total_ms"])
         total = sum(r["total_ms"] for _, r in rows)
         print(f"# argus_ktimer over one eager step, {tag}: timed kernels {1e3 * total:.1f} us in "
-              f"{sum(r['launches'] for _, r in rows)} launches (conv, bias-sum and fold-backward kernels; folds, pools, "
-              f"head and optimizer are not timed launches)")
+              f"{sum(r['launches'] for _, r in rows)} launches (conv, bias-sum and fold kernels; pools, head and "
+              f"optimizer are not timed launches)")
         print("# launches  total_us  avg_us  kernel")
         for name, r in rows:
             print(f"{r['launches']:9d} {1e3 * r['total_ms']:9.1f} {r['avg_us']:7.2f}  {name}")
@@ -102,9 +103,11 @@ def main(argv=None) -> None:
     sg = FineTuneSession(product(), B, hw, trainable=a.trainable, graph=True)
     se = FineTuneSession(product(), B, hw, trainable=a.trainable, graph=False)
     stock_model = ref.to(dev).eval()
-    if a.trainable == "head":
-        for n, p in stock_model.named_parameters():
-            p.requires_grad_(n.startswith(HEAD))
+    if a.trainable != "all":  # the head, or resnet.layerK and everything behind it in model order
+        names = [n for n, _ in stock_model.named_parameters()]
+        first = "resnet.fc.weight" if a.trainable == "head" else f"resnet.{a.trainable}.0.conv1.weight"
+        for i, p in enumerate(stock_model.parameters()):
+            p.requires_grad_(i >= names.index(first))
     params = [p for p in stock_model.parameters() if p.requires_grad]
     opt = torch.optim.Adam(params, lr=1e-4)
 
