@@ -1891,12 +1891,19 @@ static int dgrad_bn_impl(const argus_conv_desc& d, int dtype, const void* dy, co
     set_error("conv_dgrad_bn_x8: no apply prologue, addend or y recompute; BN epilogue mask mode 2 only");
     return ARGUS_ERR_ARG;
   }
-  // the persistent conv1 data gradient (conv_p1x1.hip): the same dm bits, fewer partial rows
-  if (!x8 && pol[kP1x1Dgrad] && epi && !yrec && bn->mask_mode == 3 && pro && !pro->dy_out && p1x1_ok(d, dtype) &&
+  // the persistent conv1 data gradient (conv_p1x1.hip): the same dm bits, fewer partial rows. It serves a
+  // y recompute of the 64-wide blocks (y_k == d.k == 64: the yx tile rides with the A tile, both weight
+  // blocks stay in LDS at two workgroups per CU); every other recompute stays on the igemm below
+  if (!x8 && pol[kP1x1Dgrad] && epi && (!yrec || (bn->y_k == 64 && d.k == 64)) && bn->mask_mode == 3 && pro &&
+      !pro->dy_out && p1x1_ok(d, dtype) &&
       !(f8 && (pol[kFp8Passes] & 4)) && bn->workspace && bn->gamma && bn->ca && bn->cb && bn->cc &&
       (!bn->y2 || (bn->gamma2 && bn->ca2 && bn->cb2 && bn->cc2))) {
     dgrad_work(d, dtype, addend != nullptr, true, true, bn->y2 != nullptr);
     g_launch_bytes += 2.0 * d.n * d.ho * d.wo * d.k;  // the apply's y
+    if (yrec) {  // y not read: its producing conv's input instead (+ the recompute flops)
+      g_launch_bytes -= 2.0 * (double)d.n * d.h * d.w * (d.c - bn->y_k);
+      g_launch_work += 2.0 * d.n * d.h * d.w * d.c * bn->y_k;
+    }
     return p1x1_launch(d, dy, wt, dm, addend, bn, pro, st);
   }
   IgParams p;

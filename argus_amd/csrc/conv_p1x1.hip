@@ -19,6 +19,10 @@
 // output element (K in 64-element steps, two 32-k MFMAs each), the same bf16 C tile, addend and mask:
 // dm3 is bit-identical; the partial sums differ only in their summation grouping.
 //
+// The 64-wide blocks (K = 64, two workgroups per CU) can also rebuild the epilogue BN's input y3 from the
+// producing conv3's input a2 and its forward weights instead of reading it (YR below): 64 channels read
+// where 256 were, and the same bits, partial sums included.
+//
 // Reference: the backward of Bottleneck.conv1 (+ bn3 / downsample BN backward of the previous block)
 // of torchvision resnet50 (argus/models.py:43) under loss.backward() (argus/train.py:316).
 #include "common.h"
@@ -36,6 +40,11 @@ constexpr int kP1BM = 64, kP1BN = 128, kP1LDC = kP1BN + 8;
 template <int KC> ARGUS_DEV int p1_pos(int row, int chunk) {
   return row * KC + (chunk ^ (KC >= 16 ? (row & 15) : ((row >> 1) & 7)));
 }
+
+// 16-byte chunk `chunk` of row `row` of the recomputed y tile ([64][128] bf16, 16 chunks per row): the four
+// row groups g of one MFMA C fragment store (rows 4g + r, 32 contiguous bytes per group) land on four
+// distinct 32-byte bank groups; rows r and 16-row blocks stay constant offsets
+ARGUS_DEV int p1_ypos(int row, int chunk) { return row * 16 + (chunk ^ (((row >> 2) & 3) << 1)); }
 }  // namespace
 
 struct P1Params {
@@ -50,20 +59,34 @@ struct P1Params {
   int P, N, G, NB, tiles;
 };
 
-template <int K, int BW>
+// YR (K = 64): the epilogue BN's input y (bb.y, N channels) is not read but recomputed per tile as
+// y = yx * yw^T (bb.yx [P][64], the producing conv3's input a2; bb.yw [N][64], its forward weights), with the
+// forward GEMM's own accumulation (igemm_kernel: fp32 from zero, one 64-k step of two 32-k MFMAs, chunks
+// 4*s2 + g, rounded to bf16), so the bits are the ones argus_conv_fwd / argus_conv_fwd_bn_out store. The
+// workgroup's 128 rows of yw stay in LDS beside the dgrad weight block; the tile's 64 yx rows travel with
+// the A rows (loaded a tile ahead, staged in the A tile's swizzle); the y tile reuses the A / yx tile area
+// once every wave is done with those (two more barriers per tile, and one before the next tile is staged).
+template <int K, int BW, bool YR>
 __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void p1x1_dgrad_kernel(const P1Params p) {
+  static_assert(!YR || K == 64, "the recompute is built for the 64-wide blocks (two workgroups per CU)");
   constexpr bool DUAL = BW == 4;
+  constexpr int K2 = 64, KC2 = K2 / 8;  // YR: the producing conv's input channels / 16-byte chunks per row
   constexpr int KC = K / 8;           // 16-byte chunks per A / W row
   constexpr int ARP = 256 / KC;       // A rows per staging pass
   constexpr int APS = kP1BM / ARP;    // A passes (= K / 32)
   constexpr int W_B = kP1BN * K * 2, A_B = kP1BM * K * 2, C_B = kP1BM * kP1LDC * 2;
   constexpr int RED_B = 8 * 16 * 16 * 8;  // BwdEpiAcc::reduce scratch: [E][RG][CPR] float2
+  constexpr int W3_B = YR ? kP1BN * K2 * 2 : 0, X_B = YR ? kP1BM * K2 * 2 : 0;
   static_assert(C_B >= RED_B && A_B + C_B >= 256 * 32, "scratch");
-  __shared__ __attribute__((aligned(16))) u32x4 lds[(W_B + A_B + C_B) / 16];
+  static_assert(!YR || A_B + X_B >= kP1BM * kP1BN * 2, "the y tile reuses the A / yx tiles");
+  __shared__ __attribute__((aligned(16))) u32x4 lds[(W_B + W3_B + A_B + X_B + C_B) / 16];
   __shared__ int fin_flag;
   u32x4* Wl = lds;
-  u32x4* Al = lds + W_B / 16;
-  bf16* Cs = reinterpret_cast<bf16*>(lds + (W_B + A_B) / 16);
+  u32x4* W3l = lds + W_B / 16;
+  u32x4* Al = lds + (W_B + W3_B) / 16;
+  u32x4* Xl = Al + A_B / 16;
+  bf16* Cs = reinterpret_cast<bf16*>(Xl + X_B / 16);
+  u32x4* Yl = Al;  // YR: [64][128] bf16, 16 chunks per row (p1_ypos), over the A and yx tiles
 
   const int total = p.G * p.NB;
   const int wid = xcd_remap(blockIdx.x, total);  // the NB column blocks of one row split share an XCD
@@ -78,6 +101,13 @@ __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void p1x1_dgrad_kernel(const
     const int idx = tid + 256 * i, r = idx / KC, c = idx - r * KC;
     Wl[p1_pos<KC>(r, c)] = ld16(p.wd + (size_t)(nb * kP1BN + r) * K + c * 8);
   }
+  if constexpr (YR) {  // rows nb*128 .. +127 of the producing conv's forward weights
+#pragma unroll
+    for (int i = 0; i < kP1BN * KC2 / 256; ++i) {
+      const int idx = tid + 256 * i, r = idx / KC2, c = idx - r * KC2;
+      W3l[p1_pos<KC2>(r, c)] = ld16(reinterpret_cast<const bf16*>(p.bb.yw) + (size_t)(nb * kP1BN + r) * K2 + c * 8);
+    }
+  }
   // A staging: a fixed channel chunk per thread (its apply coefficients in registers)
   const int ac = tid % KC, ar0 = tid / KC;
   float ca[8], cb[8], cc[8];
@@ -90,14 +120,15 @@ __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void p1x1_dgrad_kernel(const
   BwdEpiAcc<bf16, BW> bwd;
   bwd.init(p.bb, col);
 
-  struct APre { u32x4 dm[APS], y[APS]; };
-  struct EPre { u32x4 add[4], y[4], y2[DUAL ? 4 : 1]; unsigned bits[4]; };
+  struct APre { u32x4 dm[APS], y[APS], x[YR ? APS : 1]; };  // x: the yx rows (K2 == K: the A rows' mapping)
+  struct EPre { u32x4 add[4], y[YR ? 1 : 4], y2[DUAL ? 4 : 1]; unsigned bits[4]; };
   auto load_a = [&](int t, APre& S) {
 #pragma unroll
     for (int i = 0; i < APS; ++i) {
       const int m = min(t * kP1BM + ar0 + ARP * i, p.P - 1);  // clamped; rows >= P are zeroed at staging
       S.dm[i] = ld16(p.dm + (size_t)m * K + ac * 8);
       S.y[i] = ld16(p.ay + (size_t)m * K + ac * 8);
+      if constexpr (YR) S.x[i] = ld16(reinterpret_cast<const bf16*>(p.bb.yx) + (size_t)m * K2 + ac * 8);
     }
   };
   auto load_e = [&](int t, EPre& S) {
@@ -105,7 +136,7 @@ __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void p1x1_dgrad_kernel(const
     for (int i = 0; i < 4; ++i) {
       const size_t off = (size_t)min(t * kP1BM + rg + 16 * i, p.P - 1) * p.N + col;
       if (p.addend) S.add[i] = ld16(p.addend + off);
-      S.y[i] = ld16(reinterpret_cast<const bf16*>(p.bb.y) + off);
+      if constexpr (!YR) S.y[i] = ld16(reinterpret_cast<const bf16*>(p.bb.y) + off);
       if constexpr (DUAL) S.y2[i] = ld16(reinterpret_cast<const bf16*>(p.bb.y2) + off);
       S.bits[i] = p.bb.bits[off / 8];
     }
@@ -130,6 +161,7 @@ __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void p1x1_dgrad_kernel(const
 #pragma unroll
       for (int j = 0; j < 8; ++j) d[j] = fmaf(ca[j], d[j], fmaf(cb[j], yv[j], cc[j]));
       Al[p1_pos<KC>(r, ac)] = sel(t * kP1BM + r < p.P, pack(d));
+      if constexpr (YR) Xl[p1_pos<KC2>(r, ac)] = A.x[i];  // rows >= P: a clamped row's y, never used
     }
     const int tn = t + p.G;
     if (tn < p.tiles) load_a(tn, A);  // the next tile's rows in flight during the MFMAs and the epilogue
@@ -161,6 +193,37 @@ __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void p1x1_dgrad_kernel(const
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           Cs[(32 * wm + 16 * mi + 4 * g + r) * kP1LDC + 64 * wn + 16 * ni + i16] = (bf16)acc[mi][ni][r];
+    if constexpr (YR) {
+      // ---- y tile = yx * yw^T, the forward's accumulation; through LDS to the epilogue's layout ----
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s2 = 0; s2 < K2 / 32; ++s2) {
+        const int ch = 4 * s2 + g;
+        u32x4 fa[2], fb[4];
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) fa[mi] = Xl[p1_pos<KC2>(32 * wm + 16 * mi + i16, ch)];
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) fb[ni] = W3l[p1_pos<KC2>(64 * wn + 16 * ni + i16, ch)];
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni) Mma<bf16>::run(acc[mi][ni], fa[mi], fb[ni]);
+      }
+      __syncthreads();  // every wave is done with the A and yx tiles: the y tile goes over them
+      bf16* Ys = reinterpret_cast<bf16*>(Yl);
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int cl = 64 * wn + 16 * ni + i16;
+            Ys[p1_ypos(32 * wm + 16 * mi + 4 * g + r, cl >> 3) * 8 + (cl & 7)] = (bf16)acc[mi][ni][r];
+          }
+    }
     __syncthreads();
 
     // ---- epilogue: (dx + dh) * mask -> dm3, partial sums in registers; 16-byte non-temporal stores ----
@@ -178,9 +241,13 @@ __global__ __launch_bounds__(256, K >= 256 ? 1 : 2) void p1x1_dgrad_kernel(const
         for (int j = 0; j < 8; ++j) f[j] += o[j];
         v = pack(f);
       }
-      st16_nt(p.out + (size_t)m * p.N + col, bwd.step(v, Ep.y[i], DUAL ? Ep.y2[DUAL ? i : 0] : Ep.y[i], Ep.bits[i]));
+      u32x4 yv;
+      if constexpr (YR) yv = Yl[p1_ypos(r, ec)];
+      else yv = Ep.y[i];
+      st16_nt(p.out + (size_t)m * p.N + col, bwd.step(v, yv, DUAL ? Ep.y2[DUAL ? i : 0] : yv, Ep.bits[i]));
     }
     if (tn < p.tiles) load_e(tn, Ep);
+    if constexpr (YR) __syncthreads();  // the y tile is read before the next A / yx tiles are staged over it
   }
   __syncthreads();  // the C tile area becomes the reduction scratch
   bwd.template reduce<kP1BN, 256>(p.bb, reinterpret_cast<float2*>(Cs), rg, 16, ec, (size_t)g0, p.N, nb * kP1BN);
@@ -224,6 +291,8 @@ int p1x1_launch(const argus_conv_desc& d, const void* dm, const void* wd, void* 
   p.tiles = (p.P + kP1BM - 1) / kP1BM;
   p.G = p1x1_rows(d);
   BnBwdEpi& b = p.bb;
+  const bool yr = bn->y_x != nullptr;  // (dgrad_bn_impl: y == NULL, y_w set, y_k == d.k == 64)
+  b.yx = bn->y_x; b.yw = bn->y_w; b.yk = bn->y_k;
   b.y = bn->y; b.mean = bn->mean; b.invstd = bn->invstd; b.bits = bn->mask_bits; b.y2 = bn->y2;
   b.mean2 = bn->mean2; b.invstd2 = bn->invstd2;
   b.part = reinterpret_cast<float2*>(bn->part); b.part2 = reinterpret_cast<float2*>(bn->part2);
@@ -248,15 +317,18 @@ int p1x1_launch(const argus_conv_desc& d, const void* dm, const void* wd, void* 
                                     {"argus::p1x1_dgrad_kernel<256, 3>", "argus::p1x1_dgrad_kernel<256, 4>"}};
   const int ki = d.k == 64 ? 0 : (d.k == 128 ? 1 : 2);
   const char* nm = names[ki][dual];
-  if (d.k == 64) {
-    if (dual) timed_launch(nm, p1x1_dgrad_kernel<64, 4>, grid, dim3(256), st, p);
-    else timed_launch(nm, p1x1_dgrad_kernel<64, 3>, grid, dim3(256), st, p);
+  if (yr) {
+    if (dual) timed_launch("argus::p1x1_dgrad_kernel<64, 4, true>", p1x1_dgrad_kernel<64, 4, true>, grid, dim3(256), st, p);
+    else timed_launch("argus::p1x1_dgrad_kernel<64, 3, true>", p1x1_dgrad_kernel<64, 3, true>, grid, dim3(256), st, p);
+  } else if (d.k == 64) {
+    if (dual) timed_launch(nm, p1x1_dgrad_kernel<64, 4, false>, grid, dim3(256), st, p);
+    else timed_launch(nm, p1x1_dgrad_kernel<64, 3, false>, grid, dim3(256), st, p);
   } else if (d.k == 128) {
-    if (dual) timed_launch(nm, p1x1_dgrad_kernel<128, 4>, grid, dim3(256), st, p);
-    else timed_launch(nm, p1x1_dgrad_kernel<128, 3>, grid, dim3(256), st, p);
+    if (dual) timed_launch(nm, p1x1_dgrad_kernel<128, 4, false>, grid, dim3(256), st, p);
+    else timed_launch(nm, p1x1_dgrad_kernel<128, 3, false>, grid, dim3(256), st, p);
   } else {
-    if (dual) timed_launch(nm, p1x1_dgrad_kernel<256, 4>, grid, dim3(256), st, p);
-    else timed_launch(nm, p1x1_dgrad_kernel<256, 3>, grid, dim3(256), st, p);
+    if (dual) timed_launch(nm, p1x1_dgrad_kernel<256, 4, false>, grid, dim3(256), st, p);
+    else timed_launch(nm, p1x1_dgrad_kernel<256, 3, false>, grid, dim3(256), st, p);
   }
   return check_launch("p1x1_dgrad_kernel");
 }

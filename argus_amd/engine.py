@@ -167,14 +167,22 @@ class ResNetEngine:
         # the block-output BN's backward reduction (in the epilogue of the next block's conv1 / downsample
         # data gradient) recomputes bn3's input y3 from a2 and conv3's bf16 weights instead of reading it
         # (argus_bn_bwd_epilogue.y_x; bit-identical): the 4w-channel y3 read becomes a w-channel a2 read.
-        # Measured slower (round 5, profiles/r05c_*): the recompute GEMM in the epilogue is load-latency
-        # bound, the producing dgrads took 244 / 237 us instead of 191 us (B=64; step 14.75 vs 14.06 ms)
-        self.yrec_epi = False
-        # ... and where every other reader of y3 recomputes it too (layer 1: the fused conv3 data + weight
-        # gradient, argus_conv_dgrad_wgrad_bn with pro->y NULL), y3 is never stored: the forward's fused
-        # tail writes only the block output (the debug capture keeps storing it for the stage checks);
-        # needs yrec_epi (saves ~0.1 ms at B=64 on its own: not enough to pay for it)
-        self.y3_free = False
+        # "persistent": only where the persistent conv1 data gradient serves the recompute (conv_p1x1.hip,
+        # p1x1_dgrad_kernel<64, BW, true>: a 64-wide block followed by a block without a downsample; the yx
+        # tile is loaded a tile ahead with the A rows, both weight blocks stay in LDS). True: everywhere, on
+        # the register-staged igemm's epilogue where the persistent kernel does not serve it; that
+        # recompute GEMM is load-latency bound and measured slower (round 5, profiles/r05c_*: the producing
+        # dgrads 244 / 237 us instead of 191 us at B=64; step 14.75 vs 14.06 ms). False: y3 always read.
+        # "persistent" alone is level (B=64, one process, interleaved: 13.15-13.17 vs 13.16-13.18 ms,
+        # profiles/r07a_ab_b64.txt); it pays through y3_free
+        self.yrec_epi = "persistent"
+        # ... and where every other reader of a block's y3 recomputes it too (the fused conv3 data + weight
+        # gradient, argus_conv_dgrad_wgrad_bn with pro->y NULL), that y3 is never stored nor allocated: the
+        # forward's fused tail writes only the block output (the debug capture keeps storing it for the
+        # stage checks). ResNet-50: layer 1's blocks 0 and 1. B=64: 13.07 vs 13.16-13.18 ms in one process;
+        # bench.py parent / this alternated 13.295 13.326 13.324 / 13.159 13.185 13.197 ms;
+        # 0.5 GiB less memory
+        self.y3_free = True
         # fp8: the 3x3 stride-1 convs whose forward (policy key 37 bit 8) / data gradient (bit 2) take
         # MX-fp8 operands read them as stored MX-fp8 copies (argus_conv_fwd_x8 / argus_conv_dgrad_bn_x8):
         # bn1's apply and bn2's backward apply write the e4m3 + E8M0 copy beside their bf16 output (the
@@ -251,7 +259,7 @@ class ResNetEngine:
             a = {
                 "hw_in": (h, w), "hw": (ho, wo),
                 "y1": self._t(N, h, w, b.width), "y2": self._t(N, ho, wo, b.width),
-                "y3": self._t(N, ho, wo, b.cout), "out": self._t(N, ho, wo, b.cout),
+                "y3": None, "out": self._t(N, ho, wo, b.cout),  # y3: _alloc_y3 (not where it is never stored)
                 "yd": self._t(N, ho, wo, b.cout) if b.has_ds else None,
                 "a1": self._t(N, h, w, b.width) if self.materialize else None,
                 "a2": self._t(N, ho, wo, b.width) if self.materialize else None,
@@ -346,6 +354,7 @@ class ResNetEngine:
         self.wg_ws_stem = torch.empty(wss, dtype=torch.uint8, device=self.device)
         self.stages_pro = {n: bool(L.dll.argus_conv_dgrad_stages_prologue(C.byref(cv.desc), self.cdt))
                            for n, cv in convs.items() if not cv.desc.stem}
+        self._alloc_y3()
         self.gbuf = [self._t(max_elems) for _ in range(3)]  # avgpool dh; dza / dzb (the dz of bn2 / bn1)
         # dy operands of the side-stream weight gradients come from a ring, so the main stream can
         # run ahead of the wgrad stream by several layers before it must wait to reuse a buffer
@@ -491,6 +500,7 @@ class ResNetEngine:
         if Cn != 3 * self.n_cams:
             raise ValueError(f"expected {3 * self.n_cams} input channels, got {Cn}")
         self.ensure(B, H, W)
+        self._alloc_y3()
         x = x.contiguous()
         L, dt, s = self.L, self.dt, stream()
         N = self.N
@@ -703,7 +713,7 @@ class ResNetEngine:
             dgw = wg3_apply and self.fold_fin and pf + ".conv3" in self.dgw
             if dgw:  # data + weight gradient in one pass (dW on the main stream; y3 recomputed when not stored)
                 r2 = self._dgrad_wgrad_bn(pf + ".conv3", dh, dza, pf + ".bn2", a["y2"], pf + ".bn3",
-                                          None if self._y3_free(idx) else a["y3"], a["a2"], P, G)
+                                          None if self._y3_recomputed(idx) else a["y3"], a["a2"], P, G)
                 if dy3 is not None:  # debug capture only: the fused kernel never stores dy3
                     self._bn_apply_bwd(pf + ".bn3", px_o, b.cout, dh, a["y3"], dy3)
             else:
@@ -761,7 +771,7 @@ class ResNetEngine:
             if idx > 0:
                 pb, pa = self.blocks[idx - 1], self.act[idx - 1]
                 second = (pb.prefix + ".downsample.1", pa["yd"]) if pb.has_ds else None
-                yrec = self._yrec(pb, pa)
+                yrec = self._yrec(idx - 1)
                 y3p = None if yrec else pa["y3"]
                 if b.has_ds:
                     self._dgrad_plain_or_pro(pf + ".conv1", c1_in, dx, pro1)
@@ -857,23 +867,40 @@ class ResNetEngine:
         if self.debug is not None:
             self.debug["bwd.dx"] = dx.clone()
 
-    def _y3_free(self, idx: int) -> bool:
-        """Block ``idx``'s bn3 input y3 is never stored: its forward tail is fused, the next block's
-        BN-backward epilogue recomputes it, and its conv3 backward is the fused data + weight gradient,
-        which recomputes it as well (train mode; the last block's bn3 backward reads y3)."""
-        b = self.blocks[idx]
-        c3 = b.prefix + ".conv3"
-        return (self.y3_free and self._fused_tail() and self.debug is None and idx < len(self.blocks) - 1
+    def _y3_recomputed(self, idx: int) -> bool:
+        """Every backward reader of block ``idx``'s bn3 input y3 recomputes it: the next block's BN-backward
+        epilogue (_yrec) and the block's own conv3 backward, the fused data + weight gradient (the last
+        block's bn3 backward reads y3)."""
+        c3 = self.blocks[idx].prefix + ".conv3"
+        return (self.y3_free and self._fused_tail() and idx < len(self.blocks) - 1
                 and self.fuse_apply and self.wgrad_apply and self.fold_fin and c3 in self.dgw
-                and self.stages_pro[c3] and self._yrec(b, self.act[idx]) is not None)
+                and self.stages_pro[c3] and self._yrec(idx) is not None)
 
-    def _yrec(self, blk, act):
-        """(a2, conv3's bf16 w_fwd, width) when block ``blk``'s y3 is recomputed rather than read by the
-        BN-backward epilogue that reduces its bn3 (bf16 schedule; not where the 1x1 data gradients take
-        MX-fp8 weights, policy key 37 bit 4), else None."""
+    def _y3_free(self, idx: int) -> bool:
+        """Block ``idx``'s y3 is never stored (train mode): every reader recomputes it. The debug capture
+        keeps storing it for the stage checks, which then run the benched recomputing kernels beside it."""
+        return self.debug is None and self._y3_recomputed(idx)
+
+    def _alloc_y3(self) -> None:
+        """The y3 buffers of the blocks that store it (ensure, and again before a forward: the switches
+        _y3_free reads may have changed since)."""
+        N = self.N
+        for idx, (b, a) in enumerate(zip(self.blocks, self.act)):
+            if a["y3"] is None and not self._y3_free(idx):
+                a["y3"] = self._t(N, *a["hw"], b.cout)
+
+    def _yrec(self, idx: int):
+        """(a2, conv3's bf16 w_fwd, width) when block ``idx``'s y3 is recomputed rather than read by the
+        BN-backward epilogue that reduces its bn3, in the next block's conv1 / downsample data gradient
+        (bf16 schedule; not where the 1x1 data gradients take MX-fp8 weights, policy key 37 bit 4), else
+        None. ``yrec_epi`` "persistent": only where the persistent conv1 data gradient serves the
+        recompute, a 64-wide block followed by a block without a downsample branch."""
+        blk, act = self.blocks[idx], self.act[idx]
         if not (self.yrec_epi and self.materialize and act["a2"] is not None):
             return None
         if self.cdt == FP8 and (self.tuning or {}).get(37, self.L.dll.argus_conv_policy_default(37)) & 4:
+            return None
+        if self.yrec_epi == "persistent" and (blk.width != 64 or self.blocks[idx + 1].has_ds):
             return None
         return act["a2"], self.convs[blk.prefix + ".conv3"].wf, blk.width
 

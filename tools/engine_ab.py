@@ -67,7 +67,12 @@ def main():
             if not hasattr(eng, k):  # e.g. a retired switch: never measure the defaults under its name
                 raise SystemExit(f"the engine has no attribute {k!r}")
             cur = getattr(eng, k)
-            setattr(eng, k, v == "1" if isinstance(cur, bool) else type(cur)(int(v)))
+            if not v.lstrip("-").isdigit():  # a named setting (yrec_epi=persistent)
+                setattr(eng, k, v)
+            elif isinstance(cur, (bool, str)):  # 0 / 1 switch a named setting off / fully on
+                setattr(eng, k, v == "1")
+            else:
+                setattr(eng, k, type(cur)(int(v)))
         tr = FusedTrainer(m, lr=1e-4, max_grad_norm=1.0)
         for _ in range(3):
             tr.step(images, targets)
