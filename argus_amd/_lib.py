@@ -195,6 +195,8 @@ SIGNATURES = {
     "argus_se3_loss": (_I, [_I, _P, _P, _P, _P, _F, _P]),
     "argus_se3_exp": (_I, [_I, _P, _P, _I, _P]),
     "argus_stem_infer": (_I, [_I, _I, _I, _I, _I, C.POINTER(FrameSrc), _P, _P, _P, _P, _P]),
+    "argus_frames_resample": (_I, [_I, _I, _I, _I, C.POINTER(FrameSrc), _P, _P, _P]),
+    "argus_stem_infer_roi": (_I, [_I, _I, _I, _I, _I, C.POINTER(FrameSrc), _P, _P, _P, _P, _P, _P]),
     "argus_pool_fc_gelu_workspace_bytes": (_SZ, [_I, _I, _I]),
     "argus_pool_fc_gelu": (_I, [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _SZ, _P]),
     "argus_pose_tail_workspace_bytes": (_SZ, [_I, _I]),

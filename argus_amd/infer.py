@@ -231,15 +231,19 @@ class InferenceSession:
             h, out = out, h
         return a1, self.pool[0], blocks
 
-    def _forward(self, x: torch.Tensor, probe=None) -> torch.Tensor:
-        """The launches of one forward from the contiguous (batch, 3*n_cams, H, W) tensor ``x`` into self.pred.
-        ``probe(buffer, elements)``: called after every launch that writes an activation (activation_peak)."""
-        L, dt, s, N = self.L, self.dt, stream(), self.N
-        H, W = self.hw
+    def _to_nhwc4(self, x: torch.Tensor, s) -> None:
+        """The first launch of a forward: ``x`` as the stem conv reads it, into self.x0."""
+        L, dt, N, (H, W) = self.L, self.dt, self.N, self.hw
         if x.dtype == torch.uint8:
             L.images_u8_to_nhwc4(dt, N, H, W, ptr(x), ptr(self.x0), s)
         else:
             L.images_to_nhwc4(dt, N, H, W, ptr(x), ptr(self.x0), s)
+
+    def _forward(self, x: torch.Tensor, probe=None) -> torch.Tensor:
+        """The launches of one forward from the contiguous (batch, 3*n_cams, H, W) tensor ``x`` into self.pred.
+        ``probe(buffer, elements)``: called after every launch that writes an activation (activation_peak)."""
+        L, dt, s, N = self.L, self.dt, stream(), self.N
+        self._to_nhwc4(x, s)
         y0, h, blocks = self._buffers()
         H1, W1 = self.stem_hw
         L.conv_fwd(C.byref(self.stem_desc), dt, ptr(self.x0), ptr(self.stem_wf), ptr(y0), None, None, None, s)

@@ -10,6 +10,11 @@ replay, ``batch * n_cams <= 16``, bf16 or fp16):
 - back: ``argus_pool_fc_gelu`` + ``argus_pose_tail`` replace avg-pool, fc, GELU, the three MLP GEMMs and the
   se(3) exponential, so the replay itself ends in the pose (``get_pose``, argus/utils.py:179-189).
 
+``roi=True`` gives every camera image a region of interest in source pixels (``set_roi`` / ``pose(frames,
+roi=...)``), resampled to ``hw`` inside the stem launch (``argus_stem_infer_roi``) from a device buffer that
+every replay reads: frames of any resolution, a cube anywhere in them, a tracker that follows it, without a
+resize in front of the graph and without a re-capture.
+
 The graph is stem-infer, the 52 folded convs, pool-fc-gelu, pose-tail: 55 launches where the parent session has
 61 in the graph and two more behind it. ``fused_stem=False`` / ``fused_head=False`` put the parent's launches
 back for that end (A/B timing; bisecting a mismatch to one end). Everything else (``refresh()``, the fp16 range
@@ -30,17 +35,50 @@ from argus_amd.utils import se3_exp
 MAX_ROWS = 16  # argus_pool_fc_gelu / argus_pose_tail serve batch * n_cams <= 16
 
 
+def check_roi(roi, frame_hw: tuple, hw: tuple) -> torch.Tensor:
+    """``roi`` as the float32 CPU tensor the device will read, or ValueError naming the rule it breaks.
+
+    ``roi``: ``(4,)`` or ``(batch, n_cams, 4)`` host values ``(y0, x0, height, width)`` in pixels of a
+    ``frame_hw`` frame, fractional values allowed. Served (include/argus_hip.h, argus_stem_infer_roi): finite; per
+    axis ``0 <= origin``, ``origin + extent <= frame``, ``n / 4 <= extent <= 4 n`` for the output length ``n`` of
+    ``hw``. The rules are applied to the values rounded to float32. Needs no GPU."""
+    t = torch.as_tensor(roi, dtype=torch.float64, device="cpu")
+    if t.shape[-1:] != (4,) or t.dim() not in (1, 3):
+        raise ValueError(f"roi shape: expected (4,) or (batch, n_cams, 4) values (y0, x0, height, width), got "
+                         f"{tuple(t.shape)}")
+    t = t.to(torch.float32)
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("roi finite: every value must be finite")
+    v = t.double().reshape(-1, 4)
+    for axis, name in ((0, "y"), (1, "x")):
+        o, e, S, n = v[:, axis], v[:, 2 + axis], int(frame_hw[axis]), int(hw[axis])
+        if bool((o < 0).any()):
+            raise ValueError(f"roi origin: {name}0 = {o.min().item()} is negative")
+        if bool((e < n / 4).any()) or bool((e > 4 * n).any()):
+            bad = e[(e < n / 4) | (e > 4 * n)][0].item()
+            raise ValueError(f"roi scale: the {name} extent {bad} is outside [{n / 4}, {4 * n}] (a quarter to four "
+                             f"times the network's {n})")
+        if bool((o + e > S).any()):
+            raise ValueError(f"roi inside the frame: {name}0 + extent = {(o + e).max().item()} exceeds the frame's {S}")
+    return t
+
+
 class PoseSession(InferenceSession):
     """``session.pose(frames) -> (batch, 7)`` and ``session(frames) -> (batch, 6)`` from one replay.
 
     ``hw``: the size the network sees; ``frame_hw``: the size of the frames handed in (default ``hw``), center
     cropped to ``hw`` as kornia does (``data.center_crop_slices``). ``layout``: "chw" for ``(B, 3*n_cams, Hs,
     Ws)``, "hwc" for ``(B, n_cams, Hs, Ws, 3)``. ``session.frames[dtype]`` are the static input buffers (uint8 and
-    float32): ``pose(None)`` replays on what the caller wrote there."""
+    float32): ``pose(None)`` replays on what the caller wrote there.
+
+    ``roi=True``: each camera image has a region of interest ``(y0, x0, height, width)`` in frame pixels (see
+    ``check_roi``), resampled to ``hw`` with the antialiased triangle filter of ``F.interpolate(mode="bilinear",
+    antialias=True)``. It starts as the center crop at unit scale (the bits of ``roi=False``) and is changed by
+    ``set_roi`` or ``pose(frames, roi=...)`` between replays: the graph reads it from device memory."""
 
     def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
                  graph: bool = True, frame_hw: tuple | None = None, layout: str = "chw", fused_stem: bool = True,
-                 fused_head: bool = True):
+                 fused_head: bool = True, roi: bool = False):
         _require_cuda(model)
         dtype = model.compute_dtype if compute_dtype is None else compute_dtype
         if dtype not in ("bf16", "fp16"):
@@ -53,9 +91,10 @@ class PoseSession(InferenceSession):
             raise ValueError(f"PoseSession layout is 'chw' or 'hwc', got {layout!r}")
         self.frame_hw = (int(hw[0]), int(hw[1])) if frame_hw is None else (int(frame_hw[0]), int(frame_hw[1]))
         self.layout, self.fused_stem, self.fused_head = layout, bool(fused_stem), bool(fused_head)
+        self.has_roi = bool(roi)
         if self.frame_hw[0] < hw[0] or self.frame_hw[1] < hw[1]:
             raise ValueError(f"PoseSession: frame_hw {self.frame_hw} is smaller than hw {tuple(hw)}")
-        if not self.fused_stem and (layout != "chw" or self.frame_hw != (int(hw[0]), int(hw[1]))):
+        if not self.fused_stem and not self.has_roi and (layout != "chw" or self.frame_hw != (int(hw[0]), int(hw[1]))):
             raise ValueError("PoseSession(fused_stem=False) takes pre-cropped 'chw' frames only: the 'hwc' layout "
                              "and the crop are argus_stem_infer's")
         ys, xs = center_crop_slices(self.frame_hw, hw)
@@ -101,9 +140,37 @@ class PoseSession(InferenceSession):
         self._src = {}
         for dt, t in self.frames.items():
             st = (3 * Hs * Ws, Hs * Ws, Ws, 1) if self.layout == "chw" else (3 * Hs * Ws, 1, 3 * Ws, 3)
-            self._src[dt] = FrameSrc(ptr(t), 0 if dt == torch.uint8 else 1, *st, Hs, Ws, *self.crop)
+            # with a region of interest the origin is in the region, not in the descriptor
+            self._src[dt] = FrameSrc(ptr(t), 0 if dt == torch.uint8 else 1, *st, Hs, Ws,
+                                     *((0, 0) if self.has_roi else self.crop))
+        if self.has_roi:
+            center = torch.tensor([*self.crop, *self.hw], dtype=torch.float32)
+            self._roi = center.repeat(self.N, 1).to(self.device)  # (batch * n_cams, 4): what every replay reads
+
+    # ------------------------------------------------------------------ region of interest
+    @property
+    def roi(self) -> torch.Tensor | None:
+        """The regions the next replay resamples: a (batch, n_cams, 4) float32 CPU tensor (None without ``roi``)."""
+        return self._roi.view(self.batch, self.n_cams, 4).cpu() if self.has_roi else None
+
+    def set_roi(self, roi) -> None:
+        """Validate ``roi`` (``check_roi``: ``(4,)`` for every image, or ``(batch, n_cams, 4)``) and copy it into
+        the device buffer the captured graph reads: the next replay uses it, nothing is re-captured."""
+        if not self.has_roi:
+            raise ValueError("PoseSession.set_roi: the session was built without roi=True")
+        t = check_roi(roi, self.frame_hw, self.hw)
+        if t.dim() == 3 and tuple(t.shape) != (self.batch, self.n_cams, 4):
+            raise ValueError(f"roi shape: expected (4,) or {(self.batch, self.n_cams, 4)}, got {tuple(t.shape)}")
+        with torch.cuda.device(self.device):
+            self._roi.copy_(t.expand(self.batch, self.n_cams, 4).reshape(self.N, 4))
 
     # ------------------------------------------------------------------ forward
+    def _to_nhwc4(self, x: torch.Tensor, s) -> None:
+        if not self.has_roi:
+            return super()._to_nhwc4(x, s)
+        H, W = self.hw
+        self.L.frames_resample(self.dt, self.N, H, W, C.byref(self._src[x.dtype]), ptr(self._roi), ptr(self.x0), s)
+
     def _forward(self, x: torch.Tensor, probe=None) -> torch.Tensor:
         """The launches of one forward from the static frame buffer ``x`` into self.pred and self.pose_out."""
         if not self.fused_stem:
@@ -111,8 +178,12 @@ class PoseSession(InferenceSession):
         L, dt, s, N = self.L, self.dt, stream(), self.N
         H, W = self.hw
         _, h, blocks = self._buffers()
-        L.stem_infer(dt, N, H, W, 64, C.byref(self._src[x.dtype]), ptr(self.stem_wf), ptr(self.stem_coef[0]),
-                     ptr(self.stem_coef[1]), ptr(h), s)
+        if self.has_roi:
+            L.stem_infer_roi(dt, N, H, W, 64, C.byref(self._src[x.dtype]), ptr(self._roi), ptr(self.stem_wf),
+                             ptr(self.stem_coef[0]), ptr(self.stem_coef[1]), ptr(h), s)
+        else:
+            L.stem_infer(dt, N, H, W, 64, C.byref(self._src[x.dtype]), ptr(self.stem_wf), ptr(self.stem_coef[0]),
+                         ptr(self.stem_coef[1]), ptr(h), s)
         if probe is not None:
             probe(h, N * self.pool_hw[0] * self.pool_hw[1] * 64)
         for (c1, c2, c3, ds), (a1, a2, out, yd) in zip(self.schedule, blocks):
@@ -177,14 +248,19 @@ class PoseSession(InferenceSession):
                 self._graphs["forward", dtype] = g
             g.replay()
 
-    def __call__(self, frames: torch.Tensor | None, dtype=None) -> torch.Tensor:
-        """frames (fp32 in [0, 1] or uint8 in [0, 255]) -> (batch, 6) se(3), a fresh tensor."""
+    def __call__(self, frames: torch.Tensor | None, dtype=None, roi=None) -> torch.Tensor:
+        """frames (fp32 in [0, 1] or uint8 in [0, 255]) -> (batch, 6) se(3), a fresh tensor. ``roi``: ``set_roi``
+        first."""
+        if roi is not None:
+            self.set_roi(roi)
         self._replay(frames, dtype)
         return self.pred.clone()
 
-    def pose(self, frames: torch.Tensor | None, dtype=None) -> torch.Tensor:
+    def pose(self, frames: torch.Tensor | None, dtype=None, roi=None) -> torch.Tensor:
         """(batch, 7) [t, qx, qy, qz, qw], a fresh tensor: written by the replay itself (``fused_head``), else
-        ``utils.se3_exp`` of the prediction as the parent session."""
+        ``utils.se3_exp`` of the prediction as the parent session. ``roi``: ``set_roi`` first."""
+        if roi is not None:
+            self.set_roi(roi)
         self._replay(frames, dtype)
         if not self.fused_head:
             return se3_exp(self.pred.clone())

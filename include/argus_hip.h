@@ -44,7 +44,8 @@ typedef void* argus_stream_t; /* hipStream_t */
  *   argus_conv_fwd (stem descriptor only, scale = shift = stat_part = NULL),
  *   argus_maxpool_fwd, argus_avgpool_fwd, argus_conv_fold_bn,
  *   argus_conv_infer, argus_conv_infer_splits, _max_splits, _workspace_bytes,
- *   argus_stem_infer, argus_pool_fc_gelu (and argus_pose_tail, which is fp32 and takes no dtype).
+ *   argus_stem_infer, argus_stem_infer_roi, argus_frames_resample,
+ *   argus_pool_fc_gelu (and argus_pose_tail, which is fp32 and takes no dtype).
  * Every other entry point that takes a dtype rejects it before anything is launched: the launching ones
  * return ARGUS_ERR_ARG, the planning queries their "not served" value (0, or -1 where that is their error),
  * and argus_last_error() names the dtype. There is no fp16 training path. */
@@ -679,6 +680,30 @@ typedef struct {
  * allocates or synchronises (graph-capturable); every bad argument is refused before a launch. */
 int argus_stem_infer(int out_dtype, int n_img, int h, int w, int k, const argus_frame_src* src, const void* w_fwd,
                      const float* scale, const float* shift, void* out, argus_stream_t stream);
+
+/* A region of interest per image, resampled to h x w (added at ABI 21 without a version change: detect by
+ * symbol). rois: device memory, [n_img][4] fp32 = (y0, x0, height, width) in source pixels (fractional values
+ * allowed), read by every launch, so a captured graph follows what the caller writes there. The filter is the
+ * antialiased triangle of PIL / F.interpolate(mode="bilinear", antialias=True, align_corners=False). Per axis,
+ * with source length S, output length n, origin o and extent e (pixel j covers [j, j + 1)):
+ *   s = e / n, r = max(s, 1), c_i = o + (i + 0.5) * s,
+ *   taps j = max(0, floor(c_i - r + 0.5)) .. min(S, floor(c_i + r + 0.5)) - 1,
+ *   t_ij = max(0, 1 - |j + 0.5 - c_i| / r), w_ij = t_ij / sum_j t_ij
+ * and a pixel is sum_y wy * sum_x wx * v in fp32 (uint8: v / 255.0f), rounded to T once. At unit scale and an
+ * integer origin that is the crop, bit for bit. Served (the CALLER validates: the values live on the device):
+ * finite, 0 <= o, o + e <= S, n / 4 <= e <= 4 n (at most 9 taps an axis). For any other bit pattern the result
+ * is unspecified but every read stays inside the frame. src->y0 and src->x0 must be 0 (the region holds the
+ * origin); one image's offsets over the WHOLE frame must fit 31 bits. out_dtype ARGUS_BF16 or ARGUS_F16
+ * (anything else: ARGUS_ERR_ARG, "dtype" in the message); h, w >= 8; nothing allocates or synchronises; every
+ * bad argument is refused before a launch.
+ *
+ * argus_frames_resample writes x0 (n_img, h, w, 4) of T: the NHWC4 tensor argus_images_to_nhwc4 would write
+ * for the resampled frames (channel 3 = 0). argus_stem_infer_roi is argus_stem_infer on those pixels without
+ * the tensor: the same device function fills its patch, so it equals argus_stem_infer fed x0 bit for bit. */
+int argus_frames_resample(int out_dtype, int n_img, int h, int w, const argus_frame_src* src, const float* rois,
+                          void* x0, argus_stream_t stream);
+int argus_stem_infer_roi(int out_dtype, int n_img, int h, int w, int k, const argus_frame_src* src, const float* rois,
+                         const void* w_fwd, const float* scale, const float* shift, void* out, argus_stream_t stream);
 
 /* g0[n][j] = gelu(b_fc[j] + sum_c w_fc[j][c] * mean_p x[n][p][c]): avgpool + resnet.fc + the nn.GELU() of
  * argus/models.py:85-88 in one launch (replaces argus_avgpool_fwd + argus_gemm_f32 (+ its split reduce) +
