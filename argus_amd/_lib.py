@@ -188,6 +188,7 @@ SIGNATURES = {
     "argus_arc_record_bytes": (_SZ, []),
     "argus_sample_arc_params": (_I, [_P, C.POINTER(_I), _I64, _I, _I, C.c_double, C.c_double, _P]),
     "argus_batch_gather_occlude": (_I, [_I64, _I, _I, _I, _P, _I64, _P, _P, _I, _I, _I, _P, _P]),
+    "argus_batch_gather_resample": (_I, [_I64, _I, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _I, _P, _P]),
     "argus_gemm_f32": (_I, [_I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _SZ, _P]),
     "argus_colsum_f32": (_I, [_I, _I, _P, _I, _P, _P]),
     "argus_gelu_f32": (_I, [_I64, _P, _P, _P]),

@@ -30,6 +30,7 @@
 // anything else (row heads and tails, misaligned planes) byte by byte.
 #include "common.h"
 #include "internal.h"
+#include "roi_taps.h"
 
 namespace argus {
 
@@ -161,6 +162,196 @@ __global__ __launch_bounds__(256) void gather_occlude_kernel(int n_cams, int h, 
   }
 }
 
+// ---- batch build with a region of interest per camera image (argus_batch_gather_resample) -----------------
+// out[b][cam] = the region rois[b * n_cams + cam] of the UNCROPPED frame store[index[b]][cam], occluded by its
+// arcs in source-frame coordinates, resampled to h x w with the taps of roi_axis (roi_taps.h: the deployed
+// filter of argus_frames_resample, tap for tap). A byte is (uint8) rintf(255 px) with
+// px = sum_y wy (sum_x wx v / 255.0f), each sum a chain of fmaf from 0 over ascending taps, as roi_pixel's.
+//
+// A workgroup owns an 8 x 64 output tile of one image, all three channels:
+//   1. threads 0 .. 71 build the 8 row and 64 column tap tables in LDS;
+//   2. the tile's source footprint (rows lo(first row) .. hi(last row), columns from the 16-pixel boundary at or
+//      below lo(first column)) is staged into LDS as uint8 in runs of 16 pixels; then every group of 4 staged
+//      pixels is tested against the image's arcs once (records through LDS 64 at a time, the bounding-box
+//      rejects of gather_occlude_kernel) and its covered pixels are set to 0 in LDS by the thread that owns it;
+//   3. per channel: a horizontal pass (a thread owns one column's taps in registers and every fourth footprint
+//      row) writes fp32 sums to LDS, a vertical pass (128 threads, 4 pixels each) makes the bytes; four lanes'
+//      words are gathered into one 16-byte store where the output run is whole and aligned.
+// The separable order IS the definition's order (the inner sum runs over x), so nothing is approximated. At
+// s = r = 4 the footprint has fewer than 7 s + 2 r + 1 = 37 rows and 63 s + 2 r + 1 = 261 columns (+ 15 of
+// alignment): 38 rows of 288 bytes per channel. A tap entry whose taps leave that window (no served region; any
+// other bit pattern) gets no taps: every LDS and global read stays in bounds, the pixel is unspecified.
+// LDS: 32.1 KB footprint + 9.5 KB fp32 rows of one channel + 3 KB records + 3.1 KB taps = 47.7 KB, three
+// workgroups a CU.
+constexpr int kRrH = 8, kRrW = 64;
+constexpr int kRrFH = 38;                                 // footprint rows
+constexpr int kRrFP = 288;                                // footprint row pitch, bytes: 18 runs of 16
+
+__global__ __launch_bounds__(256) void gather_resample_kernel(int n_cams, int src_h, int src_w, int h, int w, int tpr,
+                                                              int tpi, const uint8_t* __restrict__ store,
+                                                              int64_t n_samples, const int64_t* __restrict__ index,
+                                                              const float* __restrict__ rois,
+                                                              const ArcRec* __restrict__ arcs, int n_arcs,
+                                                              uint8_t* __restrict__ out) {
+  __shared__ ArcRec recs[kArcChunk];
+  __shared__ RoiTaps ty[kRrH], tx[kRrW];
+  __shared__ __attribute__((aligned(16))) uint8_t foot[3 * kRrFH * kRrFP + 16];  // + 16: taps of weight 0 past the end
+  __shared__ __attribute__((aligned(16))) float hbuf[kRrFH * kRrW];
+
+  const int tid = threadIdx.x;
+  const int64_t img = blockIdx.x / tpi;  // b * n_cams + cam
+  const int rem = (int)(blockIdx.x - img * tpi);
+  const int i0 = (rem / tpr) * kRrH, j0 = (rem % tpr) * kRrW;
+  const int nr = min(kRrH, h - i0), nc = min(kRrW, w - j0);
+  const int64_t b = img / n_cams;
+  const int cam = (int)(img - b * n_cams);
+  const int shw = src_h * src_w, ohw = h * w;
+  int64_t sample = index[b];  // clamped as gather_occlude_kernel does
+  sample = sample < 0 ? 0 : (sample >= n_samples ? n_samples - 1 : sample);
+  const uint8_t* src = store + (sample * n_cams + cam) * 3 * (int64_t)shw;
+  uint8_t* dst = out + img * 3 * (int64_t)ohw;
+
+  // ---- 1. tap tables ----
+  if (tid < kRrH + kRrW) {
+    const float* roi = rois + 4 * img;
+    const bool isrow = tid < kRrH;
+    const int k = isrow ? tid : tid - kRrH;
+    RoiTaps& t = isrow ? ty[k] : tx[k];
+    if (k < (isrow ? nr : nc)) {
+      roi_axis(isrow ? src_h : src_w, isrow ? h : w, roi[isrow ? 0 : 1], roi[isrow ? 2 : 3], (isrow ? i0 : j0) + k, t);
+    } else {  // past the image's edge: no taps
+#pragma unroll
+      for (int q = 0; q < kRoiTaps; ++q) t.w[q] = 0.f;
+      t.lo = 0;
+      t.cnt = 0;
+    }
+  }
+  __syncthreads();
+  // lo and lo + cnt do not decrease along an axis: the first entry starts the footprint, the last one ends it
+  const int fy0 = ty[0].lo, fxa = tx[0].lo & ~15;
+  const int fh = min(max(ty[nr - 1].lo + ty[nr - 1].cnt - fy0, 0), kRrFH);
+  const int fw = min(max(tx[nc - 1].lo + tx[nc - 1].cnt - fxa, 0), kRrFP);
+  const int nseg = (fw + 15) >> 4;
+
+  // ---- 2. footprint: 16-byte runs into LDS, then every group of 4 staged pixels against the arcs once ----
+  const int nq = 4 * nseg;  // groups of 4 pixels in a footprint row
+  for (int u = tid; u < fh * nseg; u += 256) {  // fy0 + fr < src_h: fh ends at a tap
+    const int fr = u / nseg, seg = u - fr * nseg;
+    const int px0 = fxa + 16 * seg, len = min(16, src_w - px0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uint8_t* s = src + ((int64_t)c * shw + (fy0 + fr) * src_w + px0);
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (len == 16 && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+        v = ld16(s);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+          if (k < len) v[k >> 2] |= (unsigned)s[k] << (8 * (k & 3));
+      }
+      *reinterpret_cast<u32x4*>(foot + ((c * kRrFH + fr) * kRrFP + 16 * seg)) = v;
+    }
+  }
+  // groups, not runs of 16: at unit scale a tile has about 60 runs but 240 groups, work for all four waves
+  for (int a0 = 0; a0 < n_arcs; a0 += kArcChunk) {
+    const int na = n_arcs - a0 < kArcChunk ? n_arcs - a0 : kArcChunk;
+    if (a0) __syncthreads();
+    {
+      const int* g = reinterpret_cast<const int*>(arcs + (img * n_arcs + a0));
+      int* l = reinterpret_cast<int*>(recs);
+      for (int k = tid; k < na * 12; k += 256) l[k] = g[k];
+    }
+    __syncthreads();  // the records, and (first chunk) the staged footprint
+    for (int q = tid; q < fh * nq; q += 256) {
+      const int fr = q / nq, qx = q - fr * nq;
+      const int py = fy0 + fr, px0 = fxa + 4 * qx, len = min(4, src_w - px0);
+      if (len <= 0) continue;
+      unsigned m = 0;  // bit k: pixel px0 + k is covered
+      for (int a = 0; a < na; ++a) {
+        const ArcRec& r = recs[a];
+        if (!arc_valid(r) || py < r.y0 || py > r.y1 || px0 + len - 1 < r.x0 || px0 > r.x1) continue;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (k < len && arc_covers(px0 + k, py, r)) m |= 1u << k;
+      }
+      if (m) {  // this thread's own words: no other thread touches them
+        const unsigned keep = ((m & 1u) ? 0u : 0xFFu) | ((m & 2u) ? 0u : 0xFF00u) | ((m & 4u) ? 0u : 0xFF0000u) |
+                              ((m & 8u) ? 0u : 0xFF000000u);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<unsigned*>(foot + ((c * kRrFH + fr) * kRrFP + 4 * qx)) &= keep;
+      }
+    }
+  }
+
+  // ---- 3. per channel: horizontal pass to fp32 rows, vertical pass to bytes ----
+  const int lane = tid & 63, wave = tid >> 6;
+  float wx[kRoiTaps];
+  int relx = tx[lane].lo - fxa, cx = tx[lane].cnt;
+  {
+    const bool ok = relx >= 0 && relx + cx <= kRrFP;
+#pragma unroll
+    for (int k = 0; k < kRoiTaps; ++k) wx[k] = ok ? tx[lane].w[k] : 0.f;
+    if (!ok) relx = 0, cx = 0;
+  }
+  int kmax = cx;  // the wave's columns differ by a tap at most: one uniform trip count, weight 0 past a column's own
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) kmax = max(kmax, __shfl_xor(kmax, off));
+  kmax = __builtin_amdgcn_readfirstlane(kmax);
+  const int vi = tid >> 4, vseg = tid & 15;  // vertical pass (tid < 128): output row, run of 4 columns
+  int rely = 0, cy = 0;
+  if (tid < 128) {
+    rely = ty[vi].lo - fy0, cy = ty[vi].cnt;
+    if (rely < 0 || rely + cy > kRrFH) rely = 0, cy = 0;
+  }
+  __syncthreads();  // the footprint is staged
+
+#pragma unroll 1
+  for (int c = 0; c < 3; ++c) {
+    const uint8_t* fc = foot + c * kRrFH * kRrFP + relx;
+    for (int r = wave; r < fh; r += 4) {
+      const uint8_t* p = fc + r * kRrFP;
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < kRoiTaps; ++k) {
+        if (k >= kmax) break;
+        acc = fmaf(wx[k], pixel_f32(p[k]), acc);
+      }
+      hbuf[r * kRrW + lane] = acc;
+    }
+    __syncthreads();
+    if (tid < 128) {
+      float px[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < cy; ++k) {
+        const float wy = ty[vi].w[k];
+        const float4 hv = *reinterpret_cast<const float4*>(hbuf + (rely + k) * kRrW + 4 * vseg);
+        px[0] = fmaf(wy, hv.x, px[0]);
+        px[1] = fmaf(wy, hv.y, px[1]);
+        px[2] = fmaf(wy, hv.z, px[2]);
+        px[3] = fmaf(wy, hv.w, px[3]);
+      }
+      unsigned v = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        v |= (unsigned)(int)fminf(fmaxf(rintf(255.0f * px[k]), 0.f), 255.f) << (8 * k);
+      const int l4 = lane & ~3;
+      const u32x4 q = {(unsigned)__shfl((int)v, l4), (unsigned)__shfl((int)v, l4 + 1), (unsigned)__shfl((int)v, l4 + 2),
+                       (unsigned)__shfl((int)v, l4 + 3)};
+      if (vi < nr) {
+        uint8_t* drow = dst + ((int64_t)c * ohw + (i0 + vi) * w + j0);
+        const int jg = 16 * (vseg >> 2);
+        if (jg + 16 <= nc && (reinterpret_cast<uintptr_t>(drow + jg) & 15) == 0) {
+          if ((lane & 3) == 0) st16(drow + jg, q);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (4 * vseg + k < nc) drow[4 * vseg + k] = (uint8_t)(v >> (8 * k));
+        }
+      }
+    }
+    if (c < 2) __syncthreads();  // hbuf is rewritten
+  }
+}
+
 // ---- host: the np.random draws of draw_spaghetti (argus/utils.py:252-275), continued from a
 // RandomState's MT19937 state. A Python loop over RandomState.randint / uniform costs about as much per
 // B=64 batch as the fused train step; this restates numpy's legacy algorithms (public: MT19937, the
@@ -251,6 +442,58 @@ int argus_batch_gather_occlude(int64_t batch, int n_cams, int h, int w, const ui
                      segs, (int)tiles, store, n_samples, index, reinterpret_cast<const ArcRec*>(arcs), n_arcs, crop_y0,
                      crop_x0, out);
   return check_launch("batch_gather_occlude");
+}
+
+int argus_batch_gather_resample(int64_t batch, int n_cams, int src_h, int src_w, int h, int w, const uint8_t* store,
+                                int64_t n_samples, const int64_t* index, const float* rois, const void* arcs,
+                                int n_arcs, uint8_t* out, argus_stream_t stream) {
+  const char* null_arg = !store ? "store" : !index ? "index" : !rois ? "rois" : !out ? "out"
+                         : (n_arcs > 0 && !arcs) ? "arcs" : nullptr;
+  if (null_arg) {
+    set_error(std::string("batch_gather_resample: ") + null_arg + " is null");
+    return ARGUS_ERR_ARG;
+  }
+  const char* size_arg = batch <= 0 ? "batch" : n_cams <= 0 ? "n_cams" : n_samples <= 0 ? "n_samples"
+                         : n_arcs < 0 ? "n_arcs" : src_h <= 0 ? "src_h" : src_w <= 0 ? "src_w" : nullptr;
+  if (size_arg) {
+    set_error(std::string("batch_gather_resample: ") + size_arg + " must be positive (n_arcs: not negative)");
+    return ARGUS_ERR_ARG;
+  }
+  if (h < 8 || w < 8) {
+    set_error("batch_gather_resample: h and w must be at least 8");
+    return ARGUS_ERR_SHAPE;
+  }
+  if (src_h > kArcFrame || src_w > kArcFrame) {
+    set_error("batch_gather_resample: src_h and src_w must not exceed 8192");
+    return ARGUS_ERR_SHAPE;
+  }
+  if (h > src_h || w > src_w) {
+    set_error("batch_gather_resample: h > src_h or w > src_w (the output is at most the frame: scale >= 1 somewhere)");
+    return ARGUS_ERR_SHAPE;
+  }
+  // the kernel indexes one image (3 planes) with 32-bit offsets
+  if (3 * (int64_t)src_h * src_w >= (1LL << 31) || 3 * (int64_t)h * w >= (1LL << 31)) {
+    set_error("batch_gather_resample: one image's offsets (3 * src_h * src_w) must fit 31 bits");
+    return ARGUS_ERR_SHAPE;
+  }
+  const int tpr = (w + kRrW - 1) / kRrW, tpi = ((h + kRrH - 1) / kRrH) * tpr;
+  const int64_t blocks = (int64_t)tpi * batch * n_cams;
+  if (blocks > 0x7FFFFFFFLL || batch > 0x7FFFFFFFLL) {
+    set_error("batch_gather_resample: batch too large for one launch");
+    return ARGUS_ERR_SHAPE;
+  }
+  {
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(store), o0 = reinterpret_cast<uintptr_t>(out);
+    const uint64_t sb = (uint64_t)n_samples * n_cams * 3 * src_h * src_w, ob = (uint64_t)batch * n_cams * 3 * h * w;
+    if (s0 < o0 + ob && o0 < s0 + sb) {
+      set_error("batch_gather_resample: out overlaps store");
+      return ARGUS_ERR_ARG;
+    }
+  }
+  hipLaunchKernelGGL(gather_resample_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_cams, src_h,
+                     src_w, h, w, tpr, tpi, store, n_samples, index, rois, reinterpret_cast<const ArcRec*>(arcs), n_arcs,
+                     out);
+  return check_launch("batch_gather_resample");
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 // from a per-image region read from device memory; frames_resample_kernel writes those pixels as the NHWC4 tensor.
 #include "internal.h"
 #include "ktimer.h"
+#include "roi_taps.h"
 #include "stem_tile.h"
 
 namespace argus {
@@ -140,32 +141,7 @@ static int stem_infer_run(const StemInferParams<T>& p, hipStream_t st, const cha
 //
 // Direct 2-D taps (at most 9 x 9, the served 1/4 <= s <= 4), no separable pass: at unit scale every pixel has
 // one tap and the kernel is stem_infer_kernel plus the tap tables.
-constexpr int kRoiTaps = 9;
-
-struct RoiTaps {
-  float w[kRoiTaps];  // normalised; 0 beyond cnt
-  int lo, cnt;        // source pixels lo .. lo + cnt - 1, inside [0, S) for ANY bit pattern of the region
-};
-
-ARGUS_DEV void roi_axis(int S, int n, float o, float e, int i, RoiTaps& out) {
-  const float s = e / (float)n, r = fmaxf(s, 1.f);
-  const float c = fmaf((float)i + 0.5f, s, o);
-  // clamped as floats (fmaxf drops a NaN), then as integers ((float)S may round up): 0 <= lo <= hi <= S
-  const float fs = (float)S;
-  const int lo = min((int)fminf(fmaxf(floorf(c - r + 0.5f), 0.f), fs), S);
-  const int hi = min((int)fminf(fmaxf(floorf(c + r + 0.5f), 0.f), fs), S);
-  const int cnt = min(max(hi - lo, 0), kRoiTaps);
-  float t[kRoiTaps], sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < kRoiTaps; ++k) {
-    t[k] = k < cnt ? fmaxf(0.f, 1.f - fabsf((float)(lo + k) + 0.5f - c) / r) : 0.f;
-    sum += t[k];
-  }
-#pragma unroll
-  for (int k = 0; k < kRoiTaps; ++k) out.w[k] = t[k] / sum;
-  out.lo = lo;
-  out.cnt = cnt;
-}
+// kRoiTaps, RoiTaps and roi_axis live in roi_taps.h (shared with resident.hip).
 
 // X: one image; offsets fit 31 bits over the whole source frame (checked by the callers' entry points)
 template <typename In>

@@ -19,10 +19,16 @@ restates it and measures its distance from PIL), drawn from the same ``np.random
 the same order as ``utils.draw_spaghetti`` (``sample_arcs``), in source-frame coordinates: the reference
 draws on the full frame and crops afterwards (data.py:131-137). The photometric augmentations stay where they
 are (``DeviceAugmentation``). There is no CPU fallback: a non-cuda device raises.
+
+``ResidentDataset(..., full_frames=True)`` keeps the uncropped frames instead, and ``ResidentLoader(...,
+roi_jitter=(lo, hi, shift))`` then builds every camera image from a random region of interest of its frame
+(``sample_rois``), occluded first and resampled with the filter ``PoseSession(roi=True)`` deploys, in one launch
+(``argus_batch_gather_resample``); the batch gains ``"roi"`` (B, n_cams, 4). Off by default.
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import time
 from typing import Optional
@@ -33,8 +39,8 @@ import torch
 from argus_amd._lib import lib, ptr, stream
 from argus_amd.data import AugmentationConfig, CameraCubePoseDataset, CameraCubePoseDatasetConfig, center_crop_slices
 
-__all__ = ["ARC_WORDS", "MAX_FRAME", "sample_arcs", "arc_records", "epoch_indices", "ResidentDataset",
-           "ResidentLoader"]
+__all__ = ["ARC_WORDS", "MAX_FRAME", "sample_arcs", "arc_records", "sample_rois", "epoch_indices",
+           "ResidentDataset", "ResidentLoader"]
 
 ARC_WORDS = 12      # int32 words of one arc record (argus_arc_record_bytes() / 4)
 MAX_FRAME = 8192    # supported source-frame side: keeps every product of the arc tests inside int64
@@ -137,6 +143,40 @@ def epoch_indices(n: int, epoch: int, shuffle: bool, seed: int = 0, rank: int = 
     return idx[rank:total:world]
 
 
+def sample_rois(rng, n_images: int, frame_hw: tuple, hw: tuple, crop_origin: tuple, scale: tuple = (1.0, 1.0),
+                shift: float = 0.0) -> np.ndarray:
+    """Random regions of interest ``(y0, x0, height, width)`` for ``n_images`` camera images of a ``frame_hw``
+    frame, resampled to the network's ``hw``: (n_images, 4) float32, every one inside ``pose_session.check_roi``'s
+    domain (what ``PoseSession(roi=True)`` serves).
+
+    Per image, three ``rng.uniform`` draws in this order: ``s = exp(uniform(ln lo, ln hi))`` for ``scale = (lo,
+    hi)``, clipped to [1/4, 4] and to ``min(Hs / h, Ws / w)`` (the extents are ``(s h, s w)``: the aspect ratio is
+    kept); ``dy = uniform(-shift, shift) * h`` and ``dx = uniform(-shift, shift) * w``, added to the center crop's
+    center (``crop_origin`` + ``hw`` / 2). The origin is clipped to [0, S - extent] per axis, and once more after
+    rounding to float32. ``scale=(1, 1), shift=0`` is the center crop exactly."""
+    Hs, Ws, h, w = int(frame_hw[0]), int(frame_hw[1]), int(hw[0]), int(hw[1])
+    lo, hi, f = float(scale[0]), float(scale[1]), float(shift)
+    if n_images < 0 or h <= 0 or w <= 0 or h > Hs or w > Ws:
+        raise ValueError("sample_rois: n_images >= 0 and 0 < hw <= frame_hw")
+    if not (0.0 < lo <= hi) or not f >= 0.0:
+        raise ValueError("sample_rois: scale = (lo, hi) with 0 < lo <= hi, shift >= 0")
+    n = int(n_images)
+    low = np.array([math.log(lo), -f, -f], dtype=np.float64)
+    high = np.array([math.log(hi), f, f], dtype=np.float64)
+    u = rng.uniform(low, high, size=(n, 3))  # row-major: image after image, s then dy then dx
+    s = np.clip(np.exp(u[:, 0]), 0.25, min(4.0, Hs / h, Ws / w))
+    size = np.array([h, w], dtype=np.float64)
+    frame = np.array([Hs, Ws], dtype=np.float64)
+    ext = np.minimum(s[:, None] * size, frame)
+    center = np.array(crop_origin, dtype=np.float64) + size / 2 + u[:, 1:] * size
+    org = np.clip(center - ext / 2, 0.0, frame - ext)
+    e32 = ext.astype(np.float32)
+    lim = frame - e32.astype(np.float64)  # >= 0: a float32 rounding cannot pass the integer S
+    o32 = np.clip(org, 0.0, lim).astype(np.float32)
+    o32 = np.where(o32.astype(np.float64) > lim, np.nextafter(o32, np.float32(-1.0)), o32)
+    return np.concatenate([np.maximum(o32, np.float32(0.0)), e32], axis=1).astype(np.float32)
+
+
 def _require_cuda(device, what: str) -> torch.device:
     device = torch.device(device)
     if device.type != "cuda":
@@ -156,16 +196,25 @@ class ResidentDataset:
     and ``crop_origin`` the crop's (y0, x0) in it (``center_crop_slices``): the arcs are drawn in source-frame
     coordinates. Raises before allocating when the store would exceed ``max_bytes`` (default:
     ``DEFAULT_FREE_SHARE`` of the free device memory). ``dataset`` overrides the decoded dataset (any
-    map-style dataset of the same samples, e.g. a ``Subset``); ``ingest_seconds`` is the one-time cost."""
+    map-style dataset of the same samples, e.g. a ``Subset``); ``ingest_seconds`` is the one-time cost.
+
+    ``full_frames=True`` keeps the UNCROPPED frames instead, ``images`` (n, 3*n_cams, Hs, Ws), decoded through
+    ``CameraCubePoseDataset`` with the crop disabled (a ``dataset`` override must then yield uncropped samples);
+    ``crop_hw`` and ``crop_origin`` keep their meaning (the network's size and the center crop's origin), and the
+    memory check uses the stored shape (a 376 x 672 two-camera sample is 1.5 MB)."""
 
     def __init__(self, cfg_dataset: CameraCubePoseDatasetConfig, cfg_aug: Optional[AugmentationConfig] = None,
                  train: bool = True, device="cuda", max_bytes: Optional[int] = None, num_workers: int = -1,
-                 dataset=None) -> None:
+                 dataset=None, full_frames: bool = False) -> None:
         self.device = _require_cuda(device, "ResidentDataset")
         self.cfg_aug = cfg_aug
         self.train = train
+        self.full_frames = bool(full_frames)
         base = CameraCubePoseDataset(cfg_dataset, cfg_aug=None, train=train, uint8=True)  # cfg_aug None: no arcs
         decode = base if dataset is None else dataset
+        if self.full_frames and dataset is None:  # the same samples with the crop disabled
+            decode = CameraCubePoseDataset(dataclasses.replace(cfg_dataset, center_crop=None), cfg_aug=None,
+                                           train=train, uint8=True)
         n = len(decode)
         if n == 0:
             raise ValueError("ResidentDataset: the split has no samples")
@@ -183,15 +232,16 @@ class ResidentDataset:
         self.crop_hw = crop
         if max(self.src_hw) > MAX_FRAME:
             raise ValueError(f"ResidentDataset: frames of {self.src_hw} exceed the supported {MAX_FRAME} a side")
-        need = n * 3 * self.n_cams * crop[0] * crop[1]
+        stored = self.src_hw if self.full_frames else crop
+        need = n * 3 * self.n_cams * stored[0] * stored[1]
         with torch.cuda.device(self.device):
             limit = int(DEFAULT_FREE_SHARE * torch.cuda.mem_get_info()[0]) if max_bytes is None else int(max_bytes)
         if need > limit:
-            raise MemoryError(f"ResidentDataset: {n} samples of {3 * self.n_cams}x{crop[0]}x{crop[1]} uint8 need "
+            raise MemoryError(f"ResidentDataset: {n} samples of {3 * self.n_cams}x{stored[0]}x{stored[1]} uint8 need "
                               f"{need} bytes on the device, over the limit of {limit}; use the DataLoader path "
                               "(CameraCubePoseDataset; train without --resident-dataset) or raise max_bytes")
         t0 = time.perf_counter()
-        self.images = torch.empty((n, 3 * self.n_cams, crop[0], crop[1]), dtype=torch.uint8, device=self.device)
+        self.images = torch.empty((n, 3 * self.n_cams, stored[0], stored[1]), dtype=torch.uint8, device=self.device)
         self.poses = torch.empty((n, 7), dtype=torch.float32, device=self.device)
         nw = MAX_DECODE_WORKERS if num_workers < 0 else min(int(num_workers), MAX_DECODE_WORKERS)
         nw = min(nw, n // 64)  # no more workers than decode batches: a spawn costs more than a small split
@@ -227,18 +277,39 @@ class ResidentLoader:
     yielded as the DataLoader's default does). Arcs are drawn for train and validation alike, as
     ``data.py`` does; ``num_spaghetti == 0`` or ``cfg_aug is None`` launches with no arcs.
 
+    A ``ResidentDataset(full_frames=True)`` is served by ``argus_batch_gather_resample`` instead: every camera
+    image is a region of interest ``(y0, x0, height, width)`` of its uncropped frame, occluded in source-frame
+    coordinates and resampled to ``crop_hw`` with the filter ``PoseSession(roi=True)`` deploys. The regions are the
+    center crop (the same bytes as the cropped store's launch) unless ``roi_jitter = (lo, hi, shift)`` draws them
+    per batch (``sample_rois``) from a generator of their own, seeded ``roi_seed + 1000003 * epoch + rank``
+    (``roi_seed`` defaults to ``arc_seed + 7919``), so the arc stream is the same with the jitter on or off. The
+    regions travel in the pinned slot between the indices and the records, and the batch gains ``"roi"``:
+    (B, n_cams, 4) fp32 on the device. ``roi_jitter`` on a cropped store raises ``ValueError``.
+
     The pinned buffers are a ring of ``RING`` slots, each guarded by an event, so the host draw of the next
     batches overlaps the device's work on the earlier ones. Yielded tensors are fresh."""
 
     RING = 4
 
     def __init__(self, ds: ResidentDataset, batch_size: int, shuffle: bool = False, seed: int = 0, rank: int = 0,
-                 world: int = 1, drop_last: bool = False, arc_seed: Optional[int] = None) -> None:
+                 world: int = 1, drop_last: bool = False, arc_seed: Optional[int] = None,
+                 roi_jitter: Optional[tuple] = None, roi_seed: Optional[int] = None) -> None:
         if not isinstance(ds, ResidentDataset):
             raise TypeError("ResidentLoader needs a ResidentDataset")
         _require_cuda(ds.device, "ResidentLoader")
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
+        self.full_frames = bool(getattr(ds, "full_frames", False))
+        if roi_jitter is not None:
+            if not self.full_frames:
+                raise ValueError("roi_jitter needs a ResidentDataset(full_frames=True): a cropped store has "
+                                 "nothing outside the center crop to resample from")
+            if len(roi_jitter) != 3:
+                raise ValueError("roi_jitter = (lo, hi, shift)")
+            roi_jitter = tuple(float(v) for v in roi_jitter)
+            if not (0.0 < roi_jitter[0] <= roi_jitter[1]) or not roi_jitter[2] >= 0.0:
+                raise ValueError("roi_jitter = (lo, hi, shift) with 0 < lo <= hi and shift >= 0")
+        self.roi_jitter = roi_jitter
         self.ds, self.batch_size, self.shuffle, self.seed = ds, int(batch_size), bool(shuffle), int(seed)
         self.rank, self.world, self.drop_last = int(rank), int(world), bool(drop_last)
         self.arc_seed = self.seed if arc_seed is None else int(arc_seed)
@@ -246,7 +317,10 @@ class ResidentLoader:
         self.n_arcs = ds.num_spaghetti
         if lib().dll.argus_arc_record_bytes() != 4 * ARC_WORDS:
             raise RuntimeError("libargus_hip arc record size != 12 int32")
-        words = 2 * self.batch_size + self.batch_size * ds.n_cams * self.n_arcs * ARC_WORDS
+        # the regions' own generator: the arc stream is the same with the jitter on or off
+        self.roi_seed = self.arc_seed + 7919 if roi_seed is None else int(roi_seed)
+        self._roi_words = 4 * ds.n_cams if self.full_frames else 0  # per sample, fp32 words in the int32 slot
+        words = self.batch_size * (2 + self._roi_words + ds.n_cams * self.n_arcs * ARC_WORDS)
         self._host = [torch.empty(words, dtype=torch.int32).pin_memory() for _ in range(self.RING)]
         self._events = [None] * self.RING
         self._slot = 0
@@ -260,10 +334,37 @@ class ResidentLoader:
     def __len__(self) -> int:
         return -(-len(self.indices()) // self.batch_size)
 
+    def host_generators(self) -> tuple:
+        """(arc generator, region generator or None) of the current epoch: ``RandomState``s seeded ``arc_seed`` /
+        ``roi_seed`` ``+ 1000003 * epoch + rank``. Two streams, so the arcs do not depend on the jitter."""
+        off = 1000003 * self.epoch + self.rank
+        rng = np.random.RandomState((self.arc_seed + off) % (1 << 32))
+        roi_rng = None if self.roi_jitter is None else np.random.RandomState((self.roi_seed + off) % (1 << 32))
+        return rng, roi_rng
+
+    def fill_slot(self, hv: np.ndarray, idx: list, rng, roi_rng) -> int:
+        """One batch's host words into the int32 array ``hv``: the int64 sample indices, the regions of a
+        full-frame store ((len(idx) * n_cams, 4) fp32: ``sample_rois`` from ``roi_rng``, the center crop when it is
+        None), the arc records from ``rng``. Returns the word offset of the records."""
+        ds, b = self.ds, len(idx)
+        a_at = b * (2 + self._roi_words)
+        hv[:2 * b].view(np.int64)[:] = idx
+        if self.full_frames:
+            hr = hv[2 * b:a_at].view(np.float32).reshape(b * ds.n_cams, 4)
+            if roi_rng is None:
+                hr[:] = np.array([*ds.crop_origin, *ds.crop_hw], dtype=np.float32)
+            else:
+                hr[:] = sample_rois(roi_rng, b * ds.n_cams, ds.src_hw, ds.crop_hw, ds.crop_origin,
+                                    self.roi_jitter[:2], self.roi_jitter[2])
+        if self.n_arcs > 0:
+            rec = arc_records(sample_arcs(rng, b * ds.n_cams, self.n_arcs, ds.src_hw))
+            hv[a_at:a_at + rec.size] = rec.reshape(-1)
+        return a_at
+
     def __iter__(self):
         ds = self.ds
         order = self.indices()
-        rng = np.random.RandomState((self.arc_seed + 1000003 * self.epoch + self.rank) % (1 << 32))
+        rng, roi_rng = self.host_generators()
         hc, wc = ds.crop_hw
         with torch.cuda.device(ds.device):
             for at in range(0, len(order), self.batch_size):
@@ -273,20 +374,24 @@ class ResidentLoader:
                 self._slot = (slot + 1) % self.RING
                 if self._events[slot] is not None:
                     self._events[slot].synchronize()  # the copy that last read this slot is done
-                used = 2 * b + b * ds.n_cams * self.n_arcs * ARC_WORDS
+                # indices, then the regions (full frames), then the arc records
+                used = b * (2 + self._roi_words + ds.n_cams * self.n_arcs * ARC_WORDS)
                 host = self._host[slot][:used]
-                hv = host.numpy()
-                hv[:2 * b].view(np.int64)[:] = idx
-                if self.n_arcs > 0:
-                    rec = arc_records(sample_arcs(rng, b * ds.n_cams, self.n_arcs, ds.src_hw))
-                    hv[2 * b:] = rec.reshape(-1)
+                a_at = self.fill_slot(host.numpy(), idx, rng, roi_rng)
                 dev = host.to(ds.device, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
                 self._events[slot] = ev
                 index = dev[:2 * b].view(torch.int64)
-                arcs = dev.data_ptr() + 8 * b if self.n_arcs > 0 else None
+                arcs = dev.data_ptr() + 4 * a_at if self.n_arcs > 0 else None
                 images = torch.empty((b, 3 * ds.n_cams, hc, wc), dtype=torch.uint8, device=ds.device)
-                lib().batch_gather_occlude(b, ds.n_cams, hc, wc, ptr(ds.images), len(ds), ptr(index), arcs,
-                                           self.n_arcs, ds.crop_origin[0], ds.crop_origin[1], ptr(images), stream())
-                yield {"images": images, "cube_pose": ds.poses.index_select(0, index)}
+                batch = {"images": images, "cube_pose": ds.poses.index_select(0, index)}
+                if self.full_frames:  # the uncropped store: every image through its region (one launch)
+                    roi = dev[2 * b:a_at].view(torch.float32).view(b, ds.n_cams, 4)
+                    lib().batch_gather_resample(b, ds.n_cams, ds.src_hw[0], ds.src_hw[1], hc, wc, ptr(ds.images),
+                                                len(ds), ptr(index), ptr(roi), arcs, self.n_arcs, ptr(images), stream())
+                    batch["roi"] = roi
+                else:
+                    lib().batch_gather_occlude(b, ds.n_cams, hc, wc, ptr(ds.images), len(ds), ptr(index), arcs,
+                                               self.n_arcs, ds.crop_origin[0], ds.crop_origin[1], ptr(images), stream())
+                yield batch

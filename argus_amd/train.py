@@ -103,10 +103,22 @@ class TrainConfig:
     # extension (--trainable {all,head,layer1..layer4}, with --freeze-bn): what the fine-tuning moves: everything,
     # the head alone, or resnet.layerK and everything behind it (the stem and the earlier stages stay frozen)
     trainable: str = "all"
+    # extension (--roi-jitter LO HI SHIFT, with --resident-dataset): the train split keeps the uncropped frames and
+    # every camera image of a batch is a random region of interest resampled on the device (resident.sample_rois:
+    # scale log-uniform in [LO, HI], center shifted by up to SHIFT of the network's size), the filter a
+    # PoseSession(roi=True) deploys. Validation keeps the center crop.
+    roi_jitter: Optional[tuple] = None
 
     def __post_init__(self) -> None:
         assert isinstance(self.save_dir, str)
         from argus_amd.finetune import TRAINABLE
+
+        if self.roi_jitter is not None:
+            if not self.resident_dataset:
+                raise ValueError("--roi-jitter needs --resident-dataset: the regions are resampled by the resident "
+                                 "loader's launch")
+            if len(self.roi_jitter) != 3:
+                raise ValueError("--roi-jitter takes three values: LO HI SHIFT")
 
         if self.trainable not in TRAINABLE:
             raise ValueError(f"trainable must be one of {', '.join(TRAINABLE)}, got {self.trainable!r}")
@@ -211,8 +223,9 @@ def make_resident_loaders(cfg: TrainConfig, device: torch.device, rank: int = 0,
     seeded from ``cfg.random_seed``. Returns (train_loader, val_loader); ``set_epoch`` is the loader's."""
     from argus_amd.resident import ResidentDataset, ResidentLoader
 
+    jitter = cfg.roi_jitter  # the train split alone keeps full frames and draws regions
     train_ds = ResidentDataset(cfg.dataset_config, cfg.augmentation_config, train=True, device=device,
-                               num_workers=cfg.num_workers)
+                               num_workers=cfg.num_workers, full_frames=jitter is not None)
     val_ds = ResidentDataset(cfg.dataset_config, cfg.augmentation_config, train=False, device=device,
                              num_workers=cfg.num_workers)
     if world > 1:
@@ -221,7 +234,7 @@ def make_resident_loaders(cfg: TrainConfig, device: torch.device, rank: int = 0,
     # DistributedSampler's default seed when sharded; a lone DataLoader shuffles from the global torch
     # generator, here the order is seeded
     train_loader = ResidentLoader(train_ds, cfg.batch_size, shuffle=True, seed=0 if world > 1 else cfg.random_seed,
-                                  **kw)
+                                  roi_jitter=jitter, **kw)
     val_loader = ResidentLoader(val_ds, cfg.batch_size, shuffle=False, seed=0, **kw)
     return train_loader, val_loader
 
@@ -406,6 +419,11 @@ def parse_args(argv=None) -> TrainConfig:
         ap.error("--dataset-config.dataset-path is required")
     if ns.get("freeze_bn") and ns.get("multigpu"):
         ap.error("--freeze-bn is single-process: frozen-BatchNorm fine-tuning is not data-parallel (drop --multigpu)")
+    if ns.get("roi_jitter") is not None:
+        if not ns.get("resident_dataset"):
+            ap.error("--roi-jitter needs --resident-dataset: the regions are resampled by the resident loader's launch")
+        if len(ns["roi_jitter"]) != 3:
+            ap.error("--roi-jitter takes three values: LO HI SHIFT")
     if ns.get("float32_matmul_precision") not in (None, "highest", "high"):
         ap.error("--float32-matmul-precision must be 'highest' or 'high'")
     from argus_amd.finetune import TRAINABLE

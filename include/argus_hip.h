@@ -767,6 +767,27 @@ int argus_sample_arc_params(uint32_t* mt_key, int* mt_pos, int64_t n_arcs, int s
 int argus_batch_gather_occlude(int64_t batch, int n_cams, int h, int w, const uint8_t* store, int64_t n_samples,
                                const int64_t* index, const void* arcs, int n_arcs, int crop_y0, int crop_x0,
                                uint8_t* out, argus_stream_t stream);
+/* argus_batch_gather_resample (added at ABI 21 without a version change: detect by symbol): the training
+ * counterpart of argus_frames_resample. One launch builds a batch from UNCROPPED uint8 frames kept in device
+ * memory, each camera image through a region of interest of its own. store: (n_samples, 3*n_cams, src_h, src_w)
+ * planar uint8; index: as argus_batch_gather_occlude's, clamped the same way; rois: device memory,
+ * [batch*n_cams][4] fp32 = (y0, x0, height, width) in source pixels; arcs: argus_batch_gather_occlude's records
+ * in source-frame pixels (n_arcs == 0 ignores arcs); out: (batch, 3*n_cams, h, w) uint8.
+ * One output byte: the per-axis taps and weights are those of argus_frames_resample (the formula above it: at
+ * most 9 taps, clamped into the frame for any bit pattern of the region); a source pixel covered by one of its
+ * image's arcs has value 0 and keeps its weight (the arcs are drawn on the frame, then the frame is resampled);
+ * px = sum_y wy * (sum_x wx * v / 255.0f) in fp32, the inner sum first, taps ascending, each step one fmaf from
+ * 0; the byte is (uint8) rintf(255.0f * px) clamped to [0, 255]. At unit scale and an integer origin that is
+ * argus_batch_gather_occlude on the cropped store, bit for bit. Each byte is written once, no atomics:
+ * deterministic and independent of the arc order. The CALLER validates the regions (they live on the device):
+ * finite, 0 <= o, o + e <= S, n / 4 <= e <= 4 n; for anything else the result is unspecified but every read
+ * stays inside the frame. Refused before any launch: a null pointer (ARGUS_ERR_ARG), a non-positive size
+ * (ARGUS_ERR_ARG), h or w < 8, src_h or src_w > 8192, h > src_h or w > src_w, one image's offsets not fitting
+ * 31 bits (ARGUS_ERR_SHAPE), out overlapping store (ARGUS_ERR_ARG); the message names the argument. Allocates
+ * nothing; capturable. */
+int argus_batch_gather_resample(int64_t batch, int n_cams, int src_h, int src_w, int h, int w, const uint8_t* store,
+                                int64_t n_samples, const int64_t* index, const float* rois, const void* arcs,
+                                int n_arcs, uint8_t* out, argus_stream_t stream);
 
 /* ---- optimizer step (clip_grad_norm_ + Adam, argus/train.py:232,317-320) --------------------- */
 size_t argus_sumsq_workspace_bytes(int64_t count);

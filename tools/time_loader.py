@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Time the batches of one epoch for each of the two loaders (no train step):
 
-    python tools/time_loader.py [--arm both|dataloader|resident] [--samples 4096] [--batch-size 64]
-                                [--workers 16] [--out profiles/resident_loader.txt]
+    python tools/time_loader.py [--arm both|dataloader|resident|roi] [--samples 4096] [--batch-size 64]
+                                [--workers 16] [--full-frames] [--roi-jitter LO HI SHIFT] [--rounds 3]
+                                [--out profiles/resident_loader.txt]
 
 Input: a dataset made by tests/conftest.make_dummy_dataset(..., hw=(376, 672)) (the reference's frame
 size) in a temporary directory; its ten training samples are repeated through torch.utils.data.Subset
@@ -11,7 +12,13 @@ to ``--samples`` (h5lite cannot write new HDF5 files). 256 x 256 crop, ten spagh
   dataloader  DataLoader(CameraCubePoseDataset(uint8=True)) as argus_amd.train.make_loaders builds it
               (spawned persistent workers, pinned memory), each batch copied to the device; the worker
               spawn is timed apart from the epoch
-  resident    ResidentDataset (the one-time ingest, timed apart) + ResidentLoader
+  resident    ResidentDataset (the one-time ingest, timed apart) + ResidentLoader; --full-frames keeps the
+              uncropped frames (every image through argus_batch_gather_resample, the center region) and
+              --roi-jitter LO HI SHIFT draws a random region per camera image (implies --full-frames)
+  roi         four resident loaders interleaved in one run, --rounds epochs each: (a) the cropped store,
+              (b) full frames with the center region, (c) --roi-jitter 0.5 2 0.25, (d) --roi-jitter 0.25 4 0.5;
+              per arm the samples/s of an epoch, the device span per batch (host-paced) and the device time of
+              the batch-building launch alone (100 back-to-back launches on one batch's operands)
 
 Each arm prints samples/s of one epoch, measured from the first batch request to a device synchronize
 after the last batch. The fused step consumes 4,800 samples/s (13.3 ms per B=64 step).
@@ -19,6 +26,7 @@ after the last batch. The fused step consumes 4,800 samples/s (13.3 ms per B=64 
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import sys
 import tempfile
 import time
@@ -32,9 +40,91 @@ import torch  # noqa: E402
 from torch.utils.data import DataLoader, Subset  # noqa: E402
 
 
+def roi_arms(args, cfg, aug, rep, device, say) -> None:
+    """The four resident loaders of the region-of-interest comparison, interleaved epoch by epoch."""
+    import numpy as np
+
+    from argus_amd._lib import lib, ptr, stream
+    from argus_amd.data import CameraCubePoseDataset
+    from argus_amd.resident import ARC_WORDS, ResidentDataset, ResidentLoader
+
+    base = CameraCubePoseDataset(dataclasses.replace(cfg, center_crop=None), None, train=True, uint8=True)
+    full = ResidentDataset(cfg, aug, train=True, device=device, num_workers=args.workers, dataset=Subset(base, rep),
+                           full_frames=True)
+    (y0, x0), (hc, wc) = full.crop_origin, full.crop_hw
+    crop = ResidentDataset.__new__(ResidentDataset)  # the same samples, cropped on the device: the parent's store
+    crop.__dict__.update(full.__dict__)
+    crop.full_frames = False
+    crop.images = full.images[:, :, y0:y0 + hc, x0:x0 + wc].contiguous()
+    say(f"roi arms: one ingest of the full frames {full.ingest_seconds:.2f} s ({full.images.numel() / 2**20:.0f} MiB; "
+        f"the cropped store {crop.images.numel() / 2**20:.0f} MiB is cut from it on the device)")
+    B = args.batch_size
+    arms = {
+        "(a) cropped store": ResidentLoader(crop, B, shuffle=True, seed=0),
+        "(b) full frames, center region": ResidentLoader(full, B, shuffle=True, seed=0),
+        "(c) full frames, jitter 0.5-2 shift 0.25": ResidentLoader(full, B, shuffle=True, seed=0,
+                                                                   roi_jitter=(0.5, 2.0, 0.25)),
+        "(d) full frames, jitter 0.25-4 shift 0.5": ResidentLoader(full, B, shuffle=True, seed=0,
+                                                                   roi_jitter=(0.25, 4.0, 0.5)),
+    }
+    rate, span, kern = ({k: [] for k in arms} for _ in range(3))
+    for loader in arms.values():  # untimed warm-up pass
+        for batch in loader:
+            pass
+    torch.cuda.synchronize()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for r in range(args.rounds):
+        for name, loader in arms.items():
+            loader.set_epoch(1 + r)
+            t0 = time.perf_counter()
+            ev0.record()
+            n = k = 0
+            for batch in loader:
+                n += batch["images"].shape[0]
+                k += 1
+            ev1.record()
+            torch.cuda.synchronize()
+            rate[name].append(n / (time.perf_counter() - t0))
+            span[name].append(ev0.elapsed_time(ev1) / k)
+            # the launch alone: 100 back-to-back launches on the operands of one batch of this epoch
+            ds = loader.ds
+            hv = np.zeros(B * (2 + loader._roi_words + ds.n_cams * loader.n_arcs * ARC_WORDS), dtype=np.int32)
+            rng, roi_rng = loader.host_generators()
+            a_at = loader.fill_slot(hv, loader.indices()[:B], rng, roi_rng)
+            dev = torch.from_numpy(hv).to(device)
+            out = torch.empty((B, 3 * ds.n_cams, hc, wc), dtype=torch.uint8, device=device)
+            arcs = dev.data_ptr() + 4 * a_at if loader.n_arcs else None
+
+            def launch():
+                if loader.full_frames:
+                    lib().batch_gather_resample(B, ds.n_cams, ds.src_hw[0], ds.src_hw[1], hc, wc, ptr(ds.images), len(ds),
+                                                ptr(dev), dev.data_ptr() + 8 * B, arcs, loader.n_arcs, ptr(out), stream())
+                else:
+                    lib().batch_gather_occlude(B, ds.n_cams, hc, wc, ptr(ds.images), len(ds), ptr(dev), arcs,
+                                               loader.n_arcs, y0, x0, ptr(out), stream())
+
+            for _ in range(5):
+                launch()
+            ev0.record()
+            for _ in range(100):
+                launch()
+            ev1.record()
+            torch.cuda.synchronize()
+            kern[name].append(ev0.elapsed_time(ev1) / 100)
+    step_ms = 13.2  # the fused B=64 step (DESIGN.md section 5)
+    for name in arms:
+        say(f"{name}: samples/s {' '.join(f'{v:.0f}' for v in rate[name])}; device span per batch (host-paced) "
+            f"{' '.join(f'{v:.3f}' for v in span[name])} ms; launch alone {' '.join(f'{v:.3f}' for v in kern[name])} ms "
+            f"= {100 * min(kern[name]) / step_ms:.1f} % of the {step_ms} ms step")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--arm", choices=("both", "dataloader", "resident"), default="both")
+    ap.add_argument("--arm", choices=("both", "dataloader", "resident", "roi"), default="both")
+    ap.add_argument("--full-frames", action="store_true", help="resident arm: keep the uncropped frames")
+    ap.add_argument("--roi-jitter", type=float, nargs=3, metavar=("LO", "HI", "SHIFT"), default=None,
+                    help="resident arm: a random region of interest per camera image (implies --full-frames)")
+    ap.add_argument("--rounds", type=int, default=3, help="roi arm: timed epochs per loader")
     ap.add_argument("--samples", type=int, default=4096)
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--workers", type=int, default=16)
@@ -88,10 +178,16 @@ def main() -> None:
             del loader
 
         if args.arm in ("both", "resident"):
-            base = CameraCubePoseDataset(cfg, None, train=True, uint8=True)
+            full = args.full_frames or args.roi_jitter is not None
+            base = CameraCubePoseDataset(dataclasses.replace(cfg, center_crop=None) if full else cfg, None, train=True,
+                                         uint8=True)
             rds = ResidentDataset(cfg, aug, train=True, device=device, num_workers=args.workers,
-                                  dataset=Subset(base, rep))
-            loader = ResidentLoader(rds, args.batch_size, shuffle=True, seed=0)
+                                  dataset=Subset(base, rep), full_frames=full)
+            loader = ResidentLoader(rds, args.batch_size, shuffle=True, seed=0,
+                                    roi_jitter=None if args.roi_jitter is None else tuple(args.roi_jitter))
+            if full:
+                say(f"resident arm: full frames {rds.src_hw[0]}x{rds.src_hw[1]}, regions "
+                    f"{'the center crop' if args.roi_jitter is None else 'jitter ' + str(tuple(args.roi_jitter))}")
             for batch in loader:  # untimed warm-up pass: first-launch and allocator costs
                 pass
             torch.cuda.synchronize()
@@ -125,6 +221,9 @@ def main() -> None:
             torch.cuda.synchronize()
             say(f"resident arm detail: host arc draw {1e3 * t_host:.3f} ms per batch; device span of an epoch "
                 f"{ev0.elapsed_time(ev1) / k:.3f} ms per batch (copy + gather/arc kernel + pose gather, host-paced)")
+
+        if args.arm == "roi":
+            roi_arms(args, cfg, aug, rep, device, say)
     if args.out:
         with open(args.out, "a") as f:
             f.write("\n".join(lines) + "\n")
