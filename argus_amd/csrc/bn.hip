@@ -187,6 +187,17 @@ static EwGeom ew_geom(int C, int E, int64_t pixels, int target_blocks) {
 // A grid target of 1024 instead of 512 blocks was slower (13.70-13.77 ms, B=256 +0.7 %).
 constexpr int kEwU = 8;
 
+// ew_geom / bwd_geometry split the C / E chunks into whole groups of min(chunks, 256): more than 256 chunks
+// that are no multiple of 256 would leave the channels past the last whole group unread and unwritten
+// (bf16 C = 2560, fp32 C = 1280), so the entry points refuse such a width before any launch.
+static bool width_unserved(int C, int E, const char* who) {
+  const int chunks = C / E;
+  if (chunks <= 256 || chunks % 256 == 0) return false;
+  set_error(std::string(who) + ": C = " + std::to_string(C) + " channels not served (more than " +
+            std::to_string(256 * E) + " channels must be a multiple of " + std::to_string(256 * E) + ")");
+  return true;
+}
+
 // MX-fp8 copy of a stored bf16 chunk (element offset off of a [P][C] tensor): 8 e4m3 bytes at out8 + off
 // and, by the first of the 4 lanes of each 32-channel block (chunk cc % 4 == 0), its E8M0 scale at
 // out8 + P*C + off / 32 (the x8 layout: argus_conv_fwd_x8)
@@ -350,12 +361,16 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(int64_t pixels, int 
     }
   }
   __shared__ float2 red[256 * 8];
-  // reduce over pixel lanes: layout red[pl][cc*E + j]
+  // reduce over pixel lanes: layout red[pl][cc*E + j]. The spare threads of a CC that does not divide 256
+  // (pl == PL, cc < 256 - PL * CC; they repeat pixels of lane 0) write no row: nothing sums it. (Their partial
+  // row would end at chunk PL * CC + (256 - PL * CC) = 256: still within red.)
   const int W = CC * E;
 #pragma unroll
   for (int br = 0; br < (DUAL ? 2 : 1); ++br) {
+    if (pl < PL) {
 #pragma unroll
-    for (int j = 0; j < E; ++j) red[pl * W + cc * E + j] = make_float2(s[j], br == 0 ? t[j] : t2[j]);
+      for (int j = 0; j < E; ++j) red[pl * W + cc * E + j] = make_float2(s[j], br == 0 ? t[j] : t2[j]);
+    }
     __syncthreads();
     float2* out = br == 0 ? part : part2;
     for (int idx = threadIdx.x; idx < W; idx += 256) {
@@ -775,6 +790,7 @@ int argus_bn_apply(int dtype, int64_t pixels, int C, const void* y, const float*
                    argus_stream_t stream) {
   if (f16_unserved(dtype, "bn_apply")) return ARGUS_ERR_ARG;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
+  if (C > 0 && C % E == 0 && width_unserved(C, E, "bn_apply")) return ARGUS_ERR_SHAPE;
   if (C % E || pixels <= 0 || !y || !scale || !shift || !out || ((rsc == nullptr) != (rsh == nullptr)) ||
       (rsc && !res)) {
     set_error("bn_apply: bad arguments");
@@ -800,6 +816,7 @@ int argus_bn_apply(int dtype, int64_t pixels, int C, const void* y, const float*
 int argus_bn_apply_x8(int64_t pixels, int C, const void* y, const float* scale, const float* shift, const void* res,
                       const float* rsc, const float* rsh, int relu, void* out, uint8_t* mask_out, void* out8,
                       argus_stream_t stream) {
+  if (C > 0 && C % 32 == 0 && width_unserved(C, 8, "bn_apply_x8")) return ARGUS_ERR_SHAPE;
   if (C % 32 || pixels <= 0 || !y || !scale || !shift || !out || !out8 || ((rsc == nullptr) != (rsh == nullptr)) ||
       (rsc && !res)) {
     set_error("bn_apply_x8: bad arguments (bf16, C a multiple of 32, out8 required)");
@@ -831,6 +848,7 @@ int argus_bn_bwd_reduce(int dtype, int64_t pixels, int C, const void* dz, int mo
   if (f16_unserved(dtype, "bn_bwd_reduce")) return ARGUS_ERR_ARG;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
   if (C % E || pixels <= 0) { set_error("bn_bwd_reduce: bad shape"); return ARGUS_ERR_SHAPE; }
+  if (width_unserved(C, E, "bn_bwd_reduce")) return ARGUS_ERR_SHAPE;
   const bool dual = y2 != nullptr;
   if (!dz || !y || !mean || !invstd || !part || mode < 0 || mode > 3 || ((mode == 1 || mode == 3) && !mask) ||
       (mode == 2 && (!scale || !shift)) || (dual && (mode == 2 || !mean2 || !invstd2 || !part2))) {
@@ -888,6 +906,7 @@ int argus_bn_bwd_apply(int dtype, int64_t pixels, int C, const void* dz, int mod
                        void* dy2, argus_stream_t stream) {
   if (f16_unserved(dtype, "bn_bwd_apply")) return ARGUS_ERR_ARG;
   const int E = dtype == ARGUS_BF16 ? 8 : 4;
+  if (C > 0 && C % E == 0 && width_unserved(C, E, "bn_bwd_apply")) return ARGUS_ERR_SHAPE;
   const bool dual = y2 != nullptr;
   if (C % E || pixels <= 0 || !dz || !y || !ca || !cb || !cc || !dy || mode < 0 || mode > 3 ||
       ((mode == 1 || mode == 3) && !mask) || (mode == 2 && (!scale || !shift)) ||
@@ -922,6 +941,7 @@ int argus_bn_bwd_apply(int dtype, int64_t pixels, int C, const void* dz, int mod
 
 int argus_bn_bwd_apply_x8(int64_t pixels, int C, const void* dm, const void* y, const float* ca, const float* cb,
                           const float* cc, void* dy, void* dy8, argus_stream_t stream) {
+  if (C > 0 && C % 32 == 0 && width_unserved(C, 8, "bn_bwd_apply_x8")) return ARGUS_ERR_SHAPE;
   if (C % 32 || pixels <= 0 || !dm || !y || !ca || !cb || !cc || !dy || !dy8) {
     set_error("bn_bwd_apply_x8: bad arguments (bf16, C a multiple of 32, dy8 required)");
     return ARGUS_ERR_ARG;

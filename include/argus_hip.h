@@ -553,7 +553,10 @@ int argus_bn_eval_coeffs(int channels, const float* gamma, const float* beta,
 /* out = [relu]( y*scale+shift + residual' ), residual' = res*res_scale+res_shift (if res_scale),
  * res (if res), else 0. out may alias y. If mask_out != NULL it also receives the ReLU mask of out:
  * one byte per 16-byte chunk (8 bf16 / 4 fp32 channels), bit j set <=> element j of the chunk > 0,
- * i.e. mask_out[(pixel*channels + c) / E] bit (c % E). */
+ * i.e. mask_out[(pixel*channels + c) / E] bit (c % E).
+ * Channels: a multiple of E; above 256 chunks (2048 bf16 / 1024 fp32 channels) a multiple of 256 chunks,
+ * else ARGUS_ERR_SHAPE before any launch. The same holds for argus_bn_apply_x8, argus_bn_bwd_reduce,
+ * argus_bn_bwd_apply and argus_bn_bwd_apply_x8. */
 int argus_bn_apply(int dtype, int64_t pixels, int channels, const void* y, const float* scale,
                    const float* shift, const void* res, const float* res_scale,
                    const float* res_shift, int relu, void* out, uint8_t* mask_out,
