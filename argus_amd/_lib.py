@@ -85,6 +85,13 @@ class FrameSrc(C.Structure):
                 ("y0", C.c_int32), ("x0", C.c_int32)]
 
 
+class TrackCfg(C.Structure):
+    """argus_track_cfg (include/argus_hip.h): the host-side settings of argus_roi_from_pose."""
+
+    _fields_ = [("half_extent", C.c_float * 3), ("margin", C.c_float), ("scale_lo", C.c_float),
+                ("scale_hi", C.c_float), ("z_near", C.c_float), ("smooth", C.c_float)]
+
+
 class FoldSrc(C.Structure):
     """argus_conv_fold_src (include/argus_hip.h): one conv of argus_conv_fold_bn_table."""
 
@@ -202,6 +209,8 @@ SIGNATURES = {
     "argus_pool_fc_gelu": (_I, [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _SZ, _P]),
     "argus_pose_tail_workspace_bytes": (_SZ, [_I, _I]),
     "argus_pose_tail": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+    "argus_roi_from_pose": (_I, [_I64, _I, _I, _I, _I, _I, _P, _I64, _P, _P, C.POINTER(TrackCfg), _P, _P, _P, _P, _P,
+                                 _P]),
     "argus_sumsq_workspace_bytes": (_SZ, [_I64]),
     "argus_global_norm": (_I, [_I64, _P, _P, _P, _P]),
     "argus_adam_step": (_I, [_I64, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P]),

@@ -18,7 +18,7 @@ CSRC = HERE / "csrc"
 OUT = HERE / "libargus_hip.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-SOURCES = ["capi.cpp", "ktimer.cpp", "conv.hip", "conv_x3.hip", "conv_glds.hip", "conv_halo.hip", "conv_dgw.hip", "conv_p1x1.hip", "conv_wgdma.hip", "conv_infer.hip", "conv_infer_bwd.hip", "conv_infer_wgrad.hip", "reduce.hip", "stem.hip", "stem_infer.hip", "stem_dgrad.hip", "bn.hip", "head.hip", "loss.hip", "optim.hip", "augment.hip", "resident.hip"]
+SOURCES = ["capi.cpp", "ktimer.cpp", "conv.hip", "conv_x3.hip", "conv_glds.hip", "conv_halo.hip", "conv_dgw.hip", "conv_p1x1.hip", "conv_wgdma.hip", "conv_infer.hip", "conv_infer_bwd.hip", "conv_infer_wgrad.hip", "reduce.hip", "stem.hip", "stem_infer.hip", "stem_dgrad.hip", "bn.hip", "head.hip", "loss.hip", "optim.hip", "augment.hip", "resident.hip", "track.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 

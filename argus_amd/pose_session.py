@@ -15,6 +15,9 @@ roi=...)``), resampled to ``hw`` inside the stem launch (``argus_stem_infer_roi`
 every replay reads: frames of any resolution, a cube anywhere in them, a tracker that follows it, without a
 resize in front of the graph and without a re-capture.
 
+``track=TrackConfig(...)`` closes the loop on the device: the graph ends with ``argus_roi_from_pose``, which writes
+the region the next replay reads from the pose this one produced (argus_amd/track.py; 56 launches).
+
 The graph is stem-infer, the 52 folded convs, pool-fc-gelu, pose-tail: 55 launches where the parent session has
 61 in the graph and two more behind it. ``fused_stem=False`` / ``fused_head=False`` put the parent's launches
 back for that end (A/B timing; bisecting a mismatch to one end). Everything else (``refresh()``, the fp16 range
@@ -30,6 +33,7 @@ from argus_amd._lib import FrameSrc, ptr, stream
 from argus_amd.data import center_crop_slices
 from argus_amd.infer import InferenceSession, _require_cuda
 from argus_amd.models import NCameraCNN
+from argus_amd.track import TrackConfig
 from argus_amd.utils import se3_exp
 
 MAX_ROWS = 16  # argus_pool_fc_gelu / argus_pose_tail serve batch * n_cams <= 16
@@ -74,11 +78,28 @@ class PoseSession(InferenceSession):
     ``roi=True``: each camera image has a region of interest ``(y0, x0, height, width)`` in frame pixels (see
     ``check_roi``), resampled to ``hw`` with the antialiased triangle filter of ``F.interpolate(mode="bilinear",
     antialias=True)``. It starts as the center crop at unit scale (the bits of ``roi=False``) and is changed by
-    ``set_roi`` or ``pose(frames, roi=...)`` between replays: the graph reads it from device memory."""
+    ``set_roi`` or ``pose(frames, roi=...)`` between replays: the graph reads it from device memory.
+
+    ``track=TrackConfig(...)`` (implies ``roi=True``; needs ``fused_head``): the forward ends with
+    ``argus_roi_from_pose`` on the pose it just wrote, in place on that buffer, so every replay aims the region the
+    next one reads at the cube: a closed-loop tracker with no host step between replays. An image whose pose puts a
+    corner behind (or too near) its camera, or is not finite, goes back to ``home``. ``last_roi`` / ``roi_valid``
+    report the region the last frame was seen through and whether the new one was aimed; ``reset_roi()`` returns to
+    ``home``; ``set_roi`` still overrides (an external detector re-acquiring the cube)."""
 
     def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
                  graph: bool = True, frame_hw: tuple | None = None, layout: str = "chw", fused_stem: bool = True,
-                 fused_head: bool = True, roi: bool = False):
+                 fused_head: bool = True, roi: bool = False, track: TrackConfig | None = None):
+        if track is not None:
+            if not isinstance(track, TrackConfig):
+                raise ValueError(f"PoseSession track: expected a TrackConfig, got {type(track).__name__}")
+            if not fused_head:
+                raise ValueError("PoseSession(track=...) needs fused_head=True: the pose has to be produced inside "
+                                 "the graph for the graph to aim the next region from it")
+            if len(track.cameras) != model.n_cams:
+                raise ValueError(f"PoseSession track: {len(track.cameras)} cameras for a model of {model.n_cams}")
+            roi = True
+        self.track = track
         _require_cuda(model)
         dtype = model.compute_dtype if compute_dtype is None else compute_dtype
         if dtype not in ("bf16", "fp16"):
@@ -105,6 +126,8 @@ class PoseSession(InferenceSession):
     def _plan(self) -> None:
         super()._plan()
         self.launches_per_forward = (1 if self.fused_stem else 3) + len(self.convs) + (2 if self.fused_head else 6)
+        if self.track is not None:
+            self.launches_per_forward += 1  # argus_roi_from_pose behind argus_pose_tail
 
     def _alloc_activations(self, max_elems: int) -> None:
         if not self.fused_stem:
@@ -146,6 +169,18 @@ class PoseSession(InferenceSession):
         if self.has_roi:
             center = torch.tensor([*self.crop, *self.hw], dtype=torch.float32)
             self._roi = center.repeat(self.N, 1).to(self.device)  # (batch * n_cams, 4): what every replay reads
+        if self.track is not None:
+            tr = self.track
+            home = center if tr.home is None else check_roi(tr.home, self.frame_hw, self.hw)
+            if home.dim() == 3 and tuple(home.shape) != (B, n, 4):
+                raise ValueError(f"TrackConfig home: expected (4,) or {(B, n, 4)}, got {tuple(home.shape)}")
+            self._home = home.expand(B, n, 4).reshape(self.N, 4).contiguous().to(self.device)
+            self._roi.copy_(self._home)
+            self._cameras = torch.from_numpy(tr.camera_words()).to(self.device)  # (n_cams, 16), uploaded once
+            self._track_cfg = tr.struct()
+            # what argus_roi_from_pose reports: the region the frame just processed was seen through, its validity
+            self._roi_used = self._home.clone()
+            self._roi_valid = torch.ones(self.N, dtype=torch.int32, device=self.device)
 
     # ------------------------------------------------------------------ region of interest
     @property
@@ -163,6 +198,25 @@ class PoseSession(InferenceSession):
             raise ValueError(f"roi shape: expected (4,) or {(self.batch, self.n_cams, 4)}, got {tuple(t.shape)}")
         with torch.cuda.device(self.device):
             self._roi.copy_(t.expand(self.batch, self.n_cams, 4).reshape(self.N, 4))
+
+    def reset_roi(self) -> None:
+        """Back to ``home`` (the center crop unless ``TrackConfig.home`` says otherwise): the next replay reads it."""
+        if self.track is None:
+            raise ValueError("PoseSession.reset_roi: the session was built without track=")
+        with torch.cuda.device(self.device):
+            self._roi.copy_(self._home)
+
+    @property
+    def last_roi(self) -> torch.Tensor | None:
+        """The regions the LAST replay resampled its frames through: (batch, n_cams, 4) float32 on the CPU (None
+        without ``track``; ``home`` before the first replay). ``roi`` is what the next one will read."""
+        return None if self.track is None else self._roi_used.view(self.batch, self.n_cams, 4).cpu()
+
+    @property
+    def roi_valid(self) -> torch.Tensor | None:
+        """(batch, n_cams) int32 on the CPU: 1 where the last replay's pose put the whole cube in front of the
+        camera and ``roi`` was aimed at it, 0 where ``roi`` fell back to ``home`` (None without ``track``)."""
+        return None if self.track is None else self._roi_valid.view(self.batch, self.n_cams).cpu()
 
     # ------------------------------------------------------------------ forward
     def _to_nhwc4(self, x: torch.Tensor, s) -> None:
@@ -209,6 +263,10 @@ class PoseSession(InferenceSession):
                     ptr(hd["output_mlp.2", "weight"]), ptr(hd["output_mlp.2", "bias"]),
                     ptr(hd["output_mlp.4", "weight"]), ptr(hd["output_mlp.4", "bias"]), ptr(self.pred),
                     ptr(self.pose_out), 0, ptr(self.tail_ws), self.tail_ws.numel(), s)
+        if self.track is not None:  # the region the NEXT forward reads, in place: the tracker's only step
+            L.roi_from_pose(B, self.n_cams, *self.frame_hw, *self.hw, ptr(self.pose_out), B, None, ptr(self._cameras),
+                            C.byref(self._track_cfg), None, ptr(self._home), ptr(self._roi), ptr(self._roi_used),
+                            ptr(self._roi_valid), s)
         return self.pred
 
     def _check_images(self, images, who: str) -> None:
@@ -239,14 +297,27 @@ class PoseSession(InferenceSession):
             if g is None:
                 side = torch.cuda.Stream(self.device)
                 side.wait_stream(torch.cuda.current_stream())
+                keep = self._tracker_state()
                 with torch.cuda.stream(side):  # untimed warm-up outside the capture
                     self._forward(x)
                 torch.cuda.current_stream().wait_stream(side)
+                self._restore_tracker(keep)  # the warm-up ran the launches for real: the tracker must not advance
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     self._forward(x)
                 self._graphs["forward", dtype] = g
             g.replay()
+
+    def _tracker_state(self):
+        """Clones of what argus_roi_from_pose writes (None without ``track``), for forwards that must not count."""
+        if self.track is None:
+            return None
+        return self._roi.clone(), self._roi_used.clone(), self._roi_valid.clone()
+
+    def _restore_tracker(self, keep) -> None:
+        if keep is not None:
+            for dst, src in zip((self._roi, self._roi_used, self._roi_valid), keep):
+                dst.copy_(src)
 
     def __call__(self, frames: torch.Tensor | None, dtype=None, roi=None) -> torch.Tensor:
         """frames (fp32 in [0, 1] or uint8 in [0, 255]) -> (batch, 6) se(3), a fresh tensor. ``roi``: ``set_roi``
@@ -278,5 +349,7 @@ class PoseSession(InferenceSession):
         with torch.cuda.device(self.device), torch.no_grad():
             x = self.frames[frames.dtype]
             x.copy_(frames)
+            keep = self._tracker_state()
             self._forward(x, probe)
+            self._restore_tracker(keep)  # a measurement, not a frame of the sequence
         return float(peak.item())

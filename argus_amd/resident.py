@@ -38,6 +38,7 @@ import torch
 
 from argus_amd._lib import lib, ptr, stream
 from argus_amd.data import AugmentationConfig, CameraCubePoseDataset, CameraCubePoseDatasetConfig, center_crop_slices
+from argus_amd.track import TrackConfig, sample_roi_jitter
 
 __all__ = ["ARC_WORDS", "MAX_FRAME", "sample_arcs", "arc_records", "sample_rois", "epoch_indices",
            "ResidentDataset", "ResidentLoader"]
@@ -286,6 +287,14 @@ class ResidentLoader:
     regions travel in the pinned slot between the indices and the records, and the batch gains ``"roi"``:
     (B, n_cams, 4) fp32 on the device. ``roi_jitter`` on a cropped store raises ``ValueError``.
 
+    ``roi_track=TrackConfig(...)`` (full frames only, as ``roi_jitter``) aims every region at the sample's labelled
+    cube instead: one ``argus_roi_from_pose`` launch over ``ds.poses`` and the batch's device indices, with ``smooth``
+    forced to 1 and the center crop as ``home``, writes the buffer the resample launch then reads: the arithmetic of
+    ``PoseSession(track=...)``, so training sees what the tracker will show. With ``roi_jitter`` as well the host
+    draws ``track.sample_roi_jitter`` (the three draws of ``sample_rois``, from the same generator) and its three
+    floats per image travel in the regions' slot; the kernel applies them around the cube. ``batch["roi"]`` is the
+    kernel's output and ``batch["roi_valid"]`` (B, n_cams) int32 says where the cube was in view (0: ``home``).
+
     The pinned buffers are a ring of ``RING`` slots, each guarded by an event, so the host draw of the next
     batches overlaps the device's work on the earlier ones. Yielded tensors are fresh."""
 
@@ -293,13 +302,23 @@ class ResidentLoader:
 
     def __init__(self, ds: ResidentDataset, batch_size: int, shuffle: bool = False, seed: int = 0, rank: int = 0,
                  world: int = 1, drop_last: bool = False, arc_seed: Optional[int] = None,
-                 roi_jitter: Optional[tuple] = None, roi_seed: Optional[int] = None) -> None:
+                 roi_jitter: Optional[tuple] = None, roi_seed: Optional[int] = None,
+                 roi_track: Optional[TrackConfig] = None) -> None:
         if not isinstance(ds, ResidentDataset):
             raise TypeError("ResidentLoader needs a ResidentDataset")
         _require_cuda(ds.device, "ResidentLoader")
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
         self.full_frames = bool(getattr(ds, "full_frames", False))
+        if roi_track is not None:
+            if not self.full_frames:
+                raise ValueError("roi_track needs a ResidentDataset(full_frames=True): a cropped store has "
+                                 "nothing outside the center crop to resample from")
+            if not isinstance(roi_track, TrackConfig):
+                raise ValueError(f"roi_track: expected a TrackConfig, got {type(roi_track).__name__}")
+            if len(roi_track.cameras) != ds.n_cams:
+                raise ValueError(f"roi_track: {len(roi_track.cameras)} cameras for a dataset of {ds.n_cams}")
+        self.roi_track = roi_track
         if roi_jitter is not None:
             if not self.full_frames:
                 raise ValueError("roi_jitter needs a ResidentDataset(full_frames=True): a cropped store has "
@@ -324,6 +343,12 @@ class ResidentLoader:
         self._host = [torch.empty(words, dtype=torch.int32).pin_memory() for _ in range(self.RING)]
         self._events = [None] * self.RING
         self._slot = 0
+        if roi_track is not None:  # uploaded once: the cameras, the home region (the center crop), the settings
+            with torch.cuda.device(ds.device):
+                self._cameras = torch.from_numpy(roi_track.camera_words()).to(ds.device)
+                home = torch.tensor([*ds.crop_origin, *ds.crop_hw], dtype=torch.float32)
+                self._home = home.repeat(self.batch_size * ds.n_cams, 1).to(ds.device)
+            self._track_cfg = roi_track.struct(smooth=1.0)  # a batch has no previous frame
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
@@ -351,7 +376,11 @@ class ResidentLoader:
         hv[:2 * b].view(np.int64)[:] = idx
         if self.full_frames:
             hr = hv[2 * b:a_at].view(np.float32).reshape(b * ds.n_cams, 4)
-            if roi_rng is None:
+            if roi_rng is not None and self.roi_track is not None:
+                # the same slot (its stride kept): 3 floats an image, packed; the tail of the slot is not read
+                hr.reshape(-1)[:3 * b * ds.n_cams] = sample_roi_jitter(roi_rng, b * ds.n_cams, self.roi_jitter[:2],
+                                                                      self.roi_jitter[2]).reshape(-1)
+            elif roi_rng is None:
                 hr[:] = np.array([*ds.crop_origin, *ds.crop_hw], dtype=np.float32)
             else:
                 hr[:] = sample_rois(roi_rng, b * ds.n_cams, ds.src_hw, ds.crop_hw, ds.crop_origin,
@@ -388,6 +417,14 @@ class ResidentLoader:
                 batch = {"images": images, "cube_pose": ds.poses.index_select(0, index)}
                 if self.full_frames:  # the uncropped store: every image through its region (one launch)
                     roi = dev[2 * b:a_at].view(torch.float32).view(b, ds.n_cams, 4)
+                    if self.roi_track is not None:  # aimed at the labelled cube: one launch in front
+                        jit = ptr(roi) if self.roi_jitter is not None else None  # the slot holds (b * n_cams, 3)
+                        roi = torch.empty((b, ds.n_cams, 4), dtype=torch.float32, device=ds.device)
+                        valid = torch.empty((b, ds.n_cams), dtype=torch.int32, device=ds.device)
+                        lib().roi_from_pose(b, ds.n_cams, ds.src_hw[0], ds.src_hw[1], hc, wc, ptr(ds.poses), len(ds),
+                                            ptr(index), ptr(self._cameras), C.byref(self._track_cfg), jit,
+                                            ptr(self._home), ptr(roi), None, ptr(valid), stream())
+                        batch["roi_valid"] = valid
                     lib().batch_gather_resample(b, ds.n_cams, ds.src_hw[0], ds.src_hw[1], hc, wc, ptr(ds.images),
                                                 len(ds), ptr(index), ptr(roi), arcs, self.n_arcs, ptr(images), stream())
                     batch["roi"] = roi

@@ -2,7 +2,7 @@
 
     python -m argus_amd.timing [--trials 100] [--batch 2] [--hw 256 256] [--dtype fp32|bf16x3|bf16]
                                [--eval] [--no-graph] [--frozen [--dtype fp16]]
-    python -m argus_amd.timing --frozen --pose [--layout hwc --frame-hw Hs Ws] [--parent] [--roi Y X H W]
+    python -m argus_amd.timing --frozen --pose [--layout hwc --frame-hw Hs Ws] [--parent] [--roi Y X H W] [--track CALIB.json]
     python -m argus_amd.timing --input-grad [--out profiles/input_grad.txt]
 
 Reference semantics (scripts/timing.py:10-48): ``NCameraCNN(n_cams=2)`` in fp32 on the GPU, left in
@@ -99,11 +99,12 @@ def forward_latency(trials: int = 100, batch: int = 2, hw=(256, 256), dtype: str
 
 def pose_latency(trials: int = 200, batch: int = 1, hw=(256, 256), dtype: str = "bf16", graph: bool = True,
                  layout: str = "chw", frame_hw=None, fused_stem: bool = True, fused_head: bool = True,
-                 parent: bool = False, device: str = "cuda", roi=None) -> dict:
+                 parent: bool = False, device: str = "cuda", roi=None, track=None) -> dict:
     """Mean / median / min seconds of one ``pose()`` call, from uint8 frames on the device to the (batch, 7) pose
     tensor, over ``trials`` timed trials. ``parent``: the yardstick arm, ``InferenceSession.pose()`` on the same
     frames (an "hwc" layout or a crop is brought to the planar cropped tensor it needs with torch ops first, as
-    argus/validate_real.py:58-75 does); else a ``PoseSession`` with the given switches."""
+    argus/validate_real.py:58-75 does); else a ``PoseSession`` with the given switches. ``track``: a
+    ``TrackConfig``: the session aims its own region from every pose (one more launch in the graph)."""
     from argus_amd.data import center_crop_slices
     from argus_amd.infer import InferenceSession
     from argus_amd.pose_session import PoseSession
@@ -126,7 +127,7 @@ def pose_latency(trials: int = 200, batch: int = 1, hw=(256, 256), dtype: str = 
             return session.pose(x)
     else:
         session = PoseSession(model, batch, (H, W), compute_dtype=dtype, graph=graph, frame_hw=(Hs, Ws), layout=layout,
-                              fused_stem=fused_stem, fused_head=fused_head, roi=roi is not None)
+                              fused_stem=fused_stem, fused_head=fused_head, roi=roi is not None, track=track)
         if roi is not None:
             session.set_roi(roi)  # once: the replays read it from the device
         run = session.pose
@@ -143,7 +144,7 @@ def pose_latency(trials: int = 200, batch: int = 1, hw=(256, 256), dtype: str = 
             "first_call_s": first, "trials": trials, "batch": batch, "hw": list(hw), "frame_hw": [Hs, Ws],
             "layout": layout, "dtype": dtype, "graph": graph, "pose": True,
             "arm": "InferenceSession" if parent else f"PoseSession(stem={int(fused_stem)},head={int(fused_head)})",
-            "launches_per_forward": session.launches_per_forward, "roi": None if roi is None else list(roi)}
+            "launches_per_forward": session.launches_per_forward, "roi": None if roi is None else list(roi), "track": track is not None}
 
 
 def _event_ms(fn, reps: int) -> float:
@@ -283,15 +284,28 @@ def main(argv=None) -> None:
     ap.add_argument("--roi", type=float, nargs=4, default=None, metavar=("Y", "X", "H", "W"),
                     help="--pose: PoseSession(roi=True) with this region of every frame (source pixels, fractional "
                          "allowed) resampled to --hw inside the stem launch")
+    ap.add_argument("--track", default=None, metavar="CALIB.json",
+                    help="--pose: PoseSession(track=load_calibration(CALIB.json)): every replay aims the next region "
+                         "from its own pose")
     a = ap.parse_args(argv)
     if a.pose:
         if not a.frozen:
             ap.error("--pose times a frozen session: pass --frozen")
+        track = None
+        if a.track:
+            if a.parent or a.unfused_head:
+                ap.error("--track needs PoseSession's fused head: not with --parent or --unfused-head")
+            from argus_amd.track import load_calibration
+
+            try:
+                track = load_calibration(a.track)
+            except (OSError, ValueError) as e:
+                ap.error(f"--track {a.track}: {e}")
         if a.roi and a.parent:
             ap.error("--roi is PoseSession's: InferenceSession (--parent) has no region of interest")
         r = pose_latency(a.trials, a.batch, tuple(a.hw), a.dtype, not a.no_graph, a.layout,
                          tuple(a.frame_hw) if a.frame_hw else None, not a.unfused_stem, not a.unfused_head, a.parent,
-                         roi=a.roi)
+                         roi=a.roi, track=track)
         print(f"pose() took {r['mean_s']} seconds on average.")
         print(json.dumps(r))
         return

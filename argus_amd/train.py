@@ -108,10 +108,18 @@ class TrainConfig:
     # scale log-uniform in [LO, HI], center shifted by up to SHIFT of the network's size), the filter a
     # PoseSession(roi=True) deploys. Validation keeps the center crop.
     roi_jitter: Optional[tuple] = None
+    # extension (--roi-track CALIB.json, with --resident-dataset): the train split's regions are aimed at each sample's
+    # labelled cube by argus_roi_from_pose from the calibration file (track.load_calibration), the arithmetic a
+    # PoseSession(track=...) deploys; --roi-jitter then jitters around the cube. Validation keeps the center crop.
+    roi_track: Optional[str] = None
 
     def __post_init__(self) -> None:
         assert isinstance(self.save_dir, str)
         from argus_amd.finetune import TRAINABLE
+
+        if self.roi_track is not None and not self.resident_dataset:
+            raise ValueError("--roi-track needs --resident-dataset: the regions are computed and resampled by the "
+                             "resident loader's launches")
 
         if self.roi_jitter is not None:
             if not self.resident_dataset:
@@ -224,8 +232,13 @@ def make_resident_loaders(cfg: TrainConfig, device: torch.device, rank: int = 0,
     from argus_amd.resident import ResidentDataset, ResidentLoader
 
     jitter = cfg.roi_jitter  # the train split alone keeps full frames and draws regions
+    track = None
+    if cfg.roi_track is not None:
+        from argus_amd.track import load_calibration
+
+        track = load_calibration(cfg.roi_track)
     train_ds = ResidentDataset(cfg.dataset_config, cfg.augmentation_config, train=True, device=device,
-                               num_workers=cfg.num_workers, full_frames=jitter is not None)
+                               num_workers=cfg.num_workers, full_frames=jitter is not None or track is not None)
     val_ds = ResidentDataset(cfg.dataset_config, cfg.augmentation_config, train=False, device=device,
                              num_workers=cfg.num_workers)
     if world > 1:
@@ -234,7 +247,7 @@ def make_resident_loaders(cfg: TrainConfig, device: torch.device, rank: int = 0,
     # DistributedSampler's default seed when sharded; a lone DataLoader shuffles from the global torch
     # generator, here the order is seeded
     train_loader = ResidentLoader(train_ds, cfg.batch_size, shuffle=True, seed=0 if world > 1 else cfg.random_seed,
-                                  roi_jitter=jitter, **kw)
+                                  roi_jitter=jitter, roi_track=track, **kw)
     val_loader = ResidentLoader(val_ds, cfg.batch_size, shuffle=False, seed=0, **kw)
     return train_loader, val_loader
 
@@ -424,6 +437,9 @@ def parse_args(argv=None) -> TrainConfig:
             ap.error("--roi-jitter needs --resident-dataset: the regions are resampled by the resident loader's launch")
         if len(ns["roi_jitter"]) != 3:
             ap.error("--roi-jitter takes three values: LO HI SHIFT")
+    if ns.get("roi_track") is not None and not ns.get("resident_dataset"):
+        ap.error("--roi-track needs --resident-dataset: the regions are computed and resampled by the resident "
+                 "loader's launches")
     if ns.get("float32_matmul_precision") not in (None, "highest", "high"):
         ap.error("--float32-matmul-precision must be 'highest' or 'high'")
     from argus_amd.finetune import TRAINABLE

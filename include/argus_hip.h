@@ -732,6 +732,50 @@ int argus_pose_tail(int batch, int d, const float* g0, const float* w0, const fl
                     const float* b2, const float* w4, const float* b4, float* pred, float* pose, int canonical_w,
                     void* workspace, size_t workspace_bytes, argus_stream_t stream);
 
+/* argus_roi_from_pose (added at ABI 21 without a version change: detect by symbol; csrc/track.hip): the region
+ * of interest of every camera image around the cube a pose places in front of the cameras, in place on the
+ * buffer argus_stem_infer_roi / argus_frames_resample / argus_batch_gather_resample read. Issued after
+ * argus_pose_tail on its pose output it closes a tracker inside a captured graph: a replay ends by writing the
+ * region the next replay reads. With index it aims a training batch's regions at the labelled cubes.
+ * poses: device, [n_poses][7] = [t(3), qx, qy, qz, qw] (argus_se3_exp's layout); sample b reads pose b, or with
+ * index (device, batch int64) pose clamp(index[b], 0, n_poses - 1). cameras: device, [n_cams][16] = [R row-major
+ * (9), t (3), fx, fy, cx, cy]: a world point X has camera coordinates Y = R X + t (+x right, +y down, +z
+ * forward) and pixel (u, v) = (fx Yx / Yz + cx, fy Yy / Yz + cy), v the row. cfg: HOST memory, read before the
+ * launch. jitter: device, [batch * n_cams][3] = (ln s, dy, dx), or NULL. home, rois, used: device,
+ * [batch * n_cams][4] = (y0, x0, height, width); valid: device, batch * n_cams int32. For image i = b * n_cams + c:
+ *   1. invalid if a pose value is non-finite or n2 = |q|^2 is 0 or non-finite; else q <- q / sqrt(n2);
+ *   2. the corners X_k = t + R(q) (+-half_extent), Y_k = R_c X_k + t_c; invalid if a Y_k is non-finite or
+ *      Y_k.z < z_near;
+ *   3. [v_min, v_max], [u_min, u_max] = the ranges of the eight pixels, (c_y, c_x) their midpoints, sigma = margin *
+ *      max((v_max - v_min) / h, (u_max - u_min) / w); invalid if one of the three is non-finite;
+ *   4. jitter: sigma <- sigma * exp(ln s), then c_y += dy * sigma * h, c_x += dx * sigma * w;
+ *   5. smooth < 1: with p = rois[i] at the start of the launch, sigma_p = p.height / h, c_p = p.origin + p.extent / 2:
+ *      sigma <- sigma_p + smooth * (sigma - sigma_p), c <- c_p + smooth * (c - c_p) (a non-finite jitter or p makes
+ *      sigma or c non-finite: the image is invalid);
+ *   6. sigma clamped to [max(scale_lo, 1/4), min(scale_hi, 4, frame_h / h, frame_w / w)] (the upper bound wins);
+ *      per axis (frame S, output n) e = min(sigma * n, S) clamped to [n / 4, min(4 n, S)], o = clamp(c - e / 2, 0,
+ *      S - e), one fp32 step down where o + e > S in double, then max(o, 0);
+ *   7. an invalid image: rois[i] = home[i];
+ *   8. valid[i] = 1 or 0, used[i] = rois[i] as it was when the launch started (either may be NULL).
+ * fp32 arithmetic, contracted to fma (tests/track_reference.py is the fp64 statement); no atomics, bit-reproducible.
+ * For ANY bit pattern of the poses a written region is home[i] or lies in the domain argus_stem_infer_roi serves
+ * (finite, 0 <= o, o + e <= S, n / 4 <= e <= 4 n): the caller validates home, nobody has to validate the pose.
+ * Refused before any launch (ARGUS_ERR_ARG, the message names the argument): a size <= 0, h or w < 8, h > frame_h
+ * or w > frame_w; null poses / cameras / cfg / home / rois; n_poses < batch without an index; a non-finite or
+ * non-positive half_extent, margin or z_near; scale_lo > scale_hi; smooth outside (0, 1]; cameras, home, rois or
+ * used not 16-byte aligned. Allocates nothing; capturable. */
+typedef struct argus_track_cfg {
+  float half_extent[3];
+  float margin;
+  float scale_lo, scale_hi;
+  float z_near;
+  float smooth;
+} argus_track_cfg;
+int argus_roi_from_pose(int64_t batch, int n_cams, int frame_h, int frame_w, int h, int w, const float* poses,
+                        int64_t n_poses, const int64_t* index, const float* cameras, const argus_track_cfg* cfg,
+                        const float* jitter, const float* home, float* rois, float* used, int32_t* valid,
+                        argus_stream_t stream);
+
 /* ---- photometric training augmentations (argus/data.py:41-103; csrc/augment.hip) -------------
  * src: uint8 images (n_img, 3, H, W) planar (a B x 6 x H x W sample batch is 2B such images);
  * dst: fp32 (same shape) = augmented src / 255; params: n_img AugParams records of

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Time the batches of one epoch for each of the two loaders (no train step):
 
-    python tools/time_loader.py [--arm both|dataloader|resident|roi] [--samples 4096] [--batch-size 64]
+    python tools/time_loader.py [--arm both|dataloader|resident|roi|roi-track] [--samples 4096] [--batch-size 64]
                                 [--workers 16] [--full-frames] [--roi-jitter LO HI SHIFT] [--rounds 3]
                                 [--out profiles/resident_loader.txt]
 
@@ -19,6 +19,8 @@ to ``--samples`` (h5lite cannot write new HDF5 files). 256 x 256 crop, ten spagh
               (b) full frames with the center region, (c) --roi-jitter 0.5 2 0.25, (d) --roi-jitter 0.25 4 0.5;
               per arm the samples/s of an epoch, the device span per batch (host-paced) and the device time of
               the batch-building launch alone (100 back-to-back launches on one batch's operands)
+  roi-track   the roi arm's (c) against the same loader with roi_track (the regions aimed at the labelled cube by one
+              argus_roi_from_pose launch in front of every batch), interleaved, and that launch alone
 
 Each arm prints samples/s of one epoch, measured from the first batch request to a device synchronize
 after the last batch. The fused step consumes 4,800 samples/s (13.3 ms per B=64 step).
@@ -118,9 +120,94 @@ def roi_arms(args, cfg, aug, rep, device, say) -> None:
             f"= {100 * min(kern[name]) / step_ms:.1f} % of the {step_ms} ms step")
 
 
+def roi_track_arms(args, cfg, aug, rep, device, say) -> None:
+    """The jittered loader of the roi arm's (c) against the same loader aimed at the labelled cube
+    (roi_track: one argus_roi_from_pose launch in front of every batch), interleaved epoch by epoch."""
+    import ctypes as C
+    import math
+
+    import numpy as np
+
+    from argus_amd._lib import lib, ptr, stream
+    from argus_amd.data import CameraCubePoseDataset
+    from argus_amd.resident import ResidentDataset, ResidentLoader
+    from argus_amd.track import Camera, TrackConfig
+
+    base = CameraCubePoseDataset(dataclasses.replace(cfg, center_crop=None), None, train=True, uint8=True)
+    full = ResidentDataset(cfg, aug, train=True, device=device, num_workers=args.workers, dataset=Subset(base, rep),
+                           full_frames=True)
+    t = full.poses[:, :3].double().cpu().numpy()
+    center, dist = t.mean(0), max(0.2, 3.0 * float(np.abs(t - t.mean(0)).max()))
+    cams = []
+    for s in (1.0, -1.0):  # two look-at cameras that see every labelled cube
+        eye = center + dist * np.array([0.0, s * 0.15, 0.13]) / math.hypot(0.15, 0.13)
+        z = (center - eye) / np.linalg.norm(center - eye)
+        x = np.cross(z, [0.0, 0.0, 1.0])
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])
+        f = (full.src_hw[0] / 2) / math.tan(math.radians(35.0))
+        cams.append(Camera(R.reshape(9), -R @ eye, f, f, full.src_hw[1] / 2, full.src_hw[0] / 2))
+    track = TrackConfig(cams, 0.035, z_near=0.02)
+    B = args.batch_size
+    jitter = (0.5, 2.0, 0.25)
+    arms = {
+        "(c) full frames, jitter 0.5-2 shift 0.25": ResidentLoader(full, B, shuffle=True, seed=0, roi_jitter=jitter),
+        "(e) roi_track, jitter 0.5-2 shift 0.25": ResidentLoader(full, B, shuffle=True, seed=0, roi_jitter=jitter,
+                                                                 roi_track=track),
+    }
+    rate, span = ({k: [] for k in arms} for _ in range(2))
+    valid = 0.0
+    for loader in arms.values():  # untimed warm-up pass
+        for batch in loader:
+            if "roi_valid" in batch:
+                valid = float(batch["roi_valid"].float().mean())
+    torch.cuda.synchronize()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for r in range(args.rounds):
+        for name, loader in arms.items():
+            loader.set_epoch(1 + r)
+            t0 = time.perf_counter()
+            ev0.record()
+            n = k = 0
+            for batch in loader:
+                n += batch["images"].shape[0]
+                k += 1
+            ev1.record()
+            torch.cuda.synchronize()
+            rate[name].append(n / (time.perf_counter() - t0))
+            span[name].append(ev0.elapsed_time(ev1) / k)
+    # the new launch alone: 100 back-to-back launches on one batch's operands
+    tl = arms["(e) roi_track, jitter 0.5-2 shift 0.25"]
+    index = torch.arange(B, dtype=torch.int64, device=device) % len(full)
+    jit = torch.zeros(B * full.n_cams, 3, dtype=torch.float32, device=device)
+    roi = torch.empty(B * full.n_cams, 4, dtype=torch.float32, device=device)
+    ok = torch.empty(B * full.n_cams, dtype=torch.int32, device=device)
+
+    def launch():
+        lib().roi_from_pose(B, full.n_cams, *full.src_hw, *full.crop_hw, ptr(full.poses), len(full), ptr(index),
+                            ptr(tl._cameras), C.byref(tl._track_cfg), ptr(jit), ptr(tl._home), ptr(roi), None, ptr(ok),
+                            stream())
+
+    kern = []
+    for _ in range(args.rounds):
+        for _ in range(5):
+            launch()
+        ev0.record()
+        for _ in range(100):
+            launch()
+        ev1.record()
+        torch.cuda.synchronize()
+        kern.append(1e3 * ev0.elapsed_time(ev1) / 100)
+    for name in arms:
+        say(f"{name}: samples/s {' '.join(f'{v:.0f}' for v in rate[name])}; device span per batch (host-paced) "
+            f"{' '.join(f'{v:.3f}' for v in span[name])} ms")
+    say(f"(e) argus_roi_from_pose alone, B={B} x {full.n_cams} images: {' '.join(f'{v:.2f}' for v in kern)} us; "
+        f"{100 * valid:.0f} % of the last warm-up batch's images valid")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--arm", choices=("both", "dataloader", "resident", "roi"), default="both")
+    ap.add_argument("--arm", choices=("both", "dataloader", "resident", "roi", "roi-track"), default="both")
     ap.add_argument("--full-frames", action="store_true", help="resident arm: keep the uncropped frames")
     ap.add_argument("--roi-jitter", type=float, nargs=3, metavar=("LO", "HI", "SHIFT"), default=None,
                     help="resident arm: a random region of interest per camera image (implies --full-frames)")
@@ -224,6 +311,8 @@ def main() -> None:
 
         if args.arm == "roi":
             roi_arms(args, cfg, aug, rep, device, say)
+        if args.arm == "roi-track":
+            roi_track_arms(args, cfg, aug, rep, device, say)
     if args.out:
         with open(args.out, "a") as f:
             f.write("\n".join(lines) + "\n")
