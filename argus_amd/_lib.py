@@ -209,6 +209,9 @@ SIGNATURES = {
     "argus_pool_fc_gelu": (_I, [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _SZ, _P]),
     "argus_pose_tail_workspace_bytes": (_SZ, [_I, _I]),
     "argus_pose_tail": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+    "argus_roi_embed": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "argus_pose_tail_roi": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ,
+                                 _P]),
     "argus_roi_from_pose": (_I, [_I64, _I, _I, _I, _I, _I, _P, _I64, _P, _P, C.POINTER(TrackCfg), _P, _P, _P, _P, _P,
                                  _P]),
     "argus_sumsq_workspace_bytes": (_SZ, [_I64]),

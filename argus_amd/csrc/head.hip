@@ -155,6 +155,61 @@ __global__ void gelu_bwd_kernel(int64_t n, const float* __restrict__ x, const fl
 }
 
 // ------------------------------------------------------------------------------------------------
+// Region-of-interest conditioning (NCameraCNNConfig.roi_frame_hw): image i = b * n_cams + c was resampled from
+// the region (y0, x0, eh, ew) of an Hs x Ws frame to the network's h x w, and output_mlp.0's pre-activation gains
+// e[b][j] = sum_k w_r[j][k] * rho[b][k] over the 4 n_cams region features
+//   rho[b][4c + 0] = (y0 + eh / 2 - Hs / 2) / Hs     rho[b][4c + 2] = ln(eh / h)
+//   rho[b][4c + 1] = (x0 + ew / 2 - Ws / 2) / Ws     rho[b][4c + 3] = ln(ew / w)
+// (rho[b] and the regions of sample b share their flat index: b * 4 n_cams + k). roi_feature is the one
+// statement of a feature and roi_embed_dot the one statement of e (from 0, fmaf, k ascending): the training
+// launch (argus_roi_embed) and the deployed tail (argus_pose_tail_roi) produce the same bits from the same
+// region. Only the feature number selects a load; nothing is indexed by a region's value.
+// ------------------------------------------------------------------------------------------------
+constexpr int kRoiMaxCams = 16;
+constexpr int kRoiMaxFeat = 4 * kRoiMaxCams;
+constexpr int kEmbedCols = 128;  // output_mlp.0's width
+
+struct RoiFrame {
+  int n_cams;
+  float frame_h, frame_w, h, w;
+};
+
+// feature f (0..3) of the region r = (y0, x0, eh, ew)
+ARGUS_DEV float roi_feature(const float* __restrict__ r, int f, const RoiFrame& F) {
+  switch (f) {
+    case 0: return (fmaf(0.5f, r[2], r[0]) - 0.5f * F.frame_h) / F.frame_h;
+    case 1: return (fmaf(0.5f, r[3], r[1]) - 0.5f * F.frame_w) / F.frame_w;
+    case 2: return logf(r[2] / F.h);
+    default: return logf(r[3] / F.w);
+  }
+}
+
+// e of column j: wr is w_r with element (j, k) at wr[j * sj + k * sk]
+ARGUS_DEV float roi_embed_dot(const float* wr, int sj, int sk, int j, const float* rho, int nfeat) {
+  float e = 0.f;
+  for (int k = 0; k < nfeat; ++k) e = fmaf(wr[j * sj + k * sk], rho[k], e);
+  return e;
+}
+
+// one workgroup of 128 threads per sample: z[b][j] += e[b][j], g = gelu(z), rho saved for the weight gradient
+__global__ __launch_bounds__(kEmbedCols) void roi_embed_kernel(RoiFrame F, const float* __restrict__ rois,
+                                                                 const float* __restrict__ w_r, float* __restrict__ z,
+                                                                 float* __restrict__ g, float* __restrict__ rho) {
+  __shared__ float rs[kRoiMaxFeat];
+  const int b = blockIdx.x, j = threadIdx.x, nfeat = 4 * F.n_cams;
+  if (j < nfeat) {
+    const float v = roi_feature(rois + (size_t)b * nfeat + (j & ~3), j & 3, F);
+    rs[j] = v;
+    if (rho) rho[(size_t)b * nfeat + j] = v;
+  }
+  __syncthreads();
+  const size_t o = (size_t)b * kEmbedCols + j;
+  const float v = z[o] + roi_embed_dot(w_r, nfeat, 1, j, rs, nfeat);
+  z[o] = v;
+  if (g) g[o] = gelu_f(v);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Frozen pose head for rows <= 16 (the deployment path: one pose per replay, latency-bound): the
 // avg-pool + resnet.fc + GELU and the output MLP + se(3) Exp in two launches, where the session had
 // avgpool_fwd, gemm_f32 (+ its split reduce), gelu and three more gemm_f32 in the graph and a clone +
@@ -168,6 +223,7 @@ constexpr int kHeadRows = 16;          // most rows (batch * n_cams, or batch) s
 constexpr int kHeadSlice = 64;         // reduction channels per workgroup
 constexpr int kHeadCols = 128;         // output columns per workgroup
 constexpr size_t kHeadTicketBytes = 256;
+static_assert(kEmbedCols == kHeadCols, "the region term is added to output_mlp.0's 128 columns");
 
 // part[row][jl] = sum over the slice's 64 channels of w[j0 + jl][c0 + .] * f[row][.] for jl < 128:
 // thread (jl = tid / 2, half = tid % 2) holds its 32 weights in registers, sums them in channel order and
@@ -256,26 +312,41 @@ __global__ __launch_bounds__(256) void pool_fc_gelu_kernel(int n, int hw, int c,
       g0[(size_t)row * rdim + j] = gelu_f(head_slice_sum(all, slices, n, row, jl) + b[j]);
 }
 
-// grid d / 64 slices of output_mlp.0; the last arriver finishes the MLP and the exponential alone
+// grid d / 64 slices of output_mlp.0; the last arriver finishes the MLP and the exponential alone. ROI
+// (argus_pose_tail_roi): the pre-activation of output_mlp.0 gains the region term e. Every workgroup stages the
+// features (batch * n_cams <= 16 regions) and w_r, transposed to [k][column], in LDS BEFORE the ticket: whichever
+// arrives last already holds them, so its critical path gains 4 n_cams LDS fmafs a column and no memory round trip.
+template <bool ROI>
 __global__ __launch_bounds__(256) void pose_tail_kernel(int batch, int d, const float* __restrict__ g0,
                                                         const float* __restrict__ w0, const float* __restrict__ b0,
                                                         const float* __restrict__ w2, const float* __restrict__ b2,
                                                         const float* __restrict__ w4, const float* __restrict__ b4,
                                                         float* __restrict__ pred, float* __restrict__ pose, int canon,
-                                                        unsigned* tickets, float* part) {
+                                                        unsigned* tickets, float* part, RoiFrame F,
+                                                        const float* __restrict__ rois, const float* __restrict__ w_r) {
   __shared__ float feat[kHeadRows][kHeadSlice];
   __shared__ float h1[kHeadRows][kHeadCols], h2[kHeadRows][kHeadCols];
   __shared__ float pr[kHeadRows * 6];
   __shared__ int flag;
+  __shared__ float rs[ROI ? kHeadRows * 4 : 1];               // rho, flat [b][4c + f]
+  __shared__ float wrs[ROI ? kRoiMaxFeat * kHeadCols : 1];    // w_r as [k][column]
   const int tid = threadIdx.x, slice = blockIdx.x, slices = gridDim.x;
+  const int nfeat = ROI ? 4 * F.n_cams : 0;
+  if constexpr (ROI) {
+    if (tid < batch * nfeat) rs[tid] = roi_feature(rois + (tid & ~3), tid & 3, F);
+    for (int i = tid; i < kHeadCols * nfeat; i += 256) wrs[(i % nfeat) * kHeadCols + i / nfeat] = w_r[i];
+  }
   for (int i = tid; i < batch * kHeadSlice; i += 256)
     feat[i / kHeadSlice][i % kHeadSlice] = g0[(size_t)(i / kHeadSlice) * d + slice * kHeadSlice + i % kHeadSlice];
   __syncthreads();
   head_slice_dot(tid, batch, w0, d, 0, slice * kHeadSlice, kHeadCols, feat, part + (size_t)slice * batch * kHeadCols);
   if (!fin_ticket<kPlainStores>(tickets, (unsigned)slices, &flag)) return;
   const int jl = tid & (kHeadCols - 1);
-  for (int row = tid >> 7; row < batch; row += 2)  // output_mlp.0 + GELU
-    h1[row][jl] = gelu_f(head_slice_sum(part, slices, batch, row, jl) + b0[jl]);
+  for (int row = tid >> 7; row < batch; row += 2) {  // output_mlp.0 (+ the region term) + GELU
+    float v = head_slice_sum(part, slices, batch, row, jl) + b0[jl];
+    if constexpr (ROI) v += roi_embed_dot(wrs, 1, kHeadCols, jl, rs + row * nfeat, nfeat);
+    h1[row][jl] = gelu_f(v);
+  }
   __syncthreads();
   for (int row = tid >> 7; row < batch; row += 2) {  // output_mlp.2 + GELU
     float s = 0.f;
@@ -408,28 +479,90 @@ size_t argus_pose_tail_workspace_bytes(int batch, int d) {
   return head_ws_bytes(batch, d, kHeadCols);
 }
 
-int argus_pose_tail(int batch, int d, const float* g0, const float* w0, const float* b0, const float* w2,
-                    const float* b2, const float* w4, const float* b4, float* pred, float* pose, int canonical_w,
-                    void* workspace, size_t workspace_bytes, argus_stream_t stream) {
+// what argus_pose_tail refuses, for both entry points (`who` prefixes the message)
+static int pose_tail_check(const char* who, int batch, int d, const float* g0, const float* w0, const float* b0,
+                           const float* w2, const float* b2, const float* w4, const float* b4, const float* pred,
+                           const float* pose, const void* workspace, size_t workspace_bytes) {
+  const std::string p = std::string(who) + ": ";
   if (!g0 || !w0 || !b0 || !w2 || !b2 || !w4 || !b4 || !pred || !pose || !workspace) {
-    set_error("pose_tail: null argument");
+    set_error(p + "null argument");
     return ARGUS_ERR_ARG;
   }
   if (batch <= 0 || batch > kHeadRows) {
-    set_error("pose_tail: serves batch 1..16 (the deployment path; larger batches use argus_gemm_f32 + argus_se3_exp)");
+    set_error(p + "serves batch 1..16 (the deployment path; larger batches use argus_gemm_f32 + argus_se3_exp)");
     return ARGUS_ERR_ARG;
   }
-  if (d <= 0) { set_error("pose_tail: bad sizes"); return ARGUS_ERR_ARG; }
-  if (d % kHeadSlice) { set_error("pose_tail: d must be a multiple of 64"); return ARGUS_ERR_SHAPE; }
+  if (d <= 0) { set_error(p + "bad sizes"); return ARGUS_ERR_ARG; }
+  if (d % kHeadSlice) { set_error(p + "d must be a multiple of 64"); return ARGUS_ERR_SHAPE; }
   if (workspace_bytes < head_ws_bytes(batch, d, kHeadCols)) {
-    set_error("pose_tail: workspace too small (argus_pose_tail_workspace_bytes)");
+    set_error(p + "workspace too small (argus_pose_tail_workspace_bytes)");
     return ARGUS_ERR_ARG;
   }
+  return ARGUS_OK;
+}
+
+// the frame / network sizes both region entry points refuse; nullptr = served
+static const char* roi_frame_refusal(int n_cams, int frame_h, int frame_w, int h, int w) {
+  if (n_cams <= 0) return "n_cams must be positive";
+  if (frame_h <= 0) return "frame_h must be positive";
+  if (frame_w <= 0) return "frame_w must be positive";
+  if (h < 8 || w < 8) return "h and w must be at least 8";
+  if (h > frame_h || w > frame_w) return "h > frame_h or w > frame_w";
+  if (n_cams > kRoiMaxCams) return "n_cams exceeds 16";
+  return nullptr;
+}
+
+int argus_pose_tail(int batch, int d, const float* g0, const float* w0, const float* b0, const float* w2,
+                    const float* b2, const float* w4, const float* b4, float* pred, float* pose, int canonical_w,
+                    void* workspace, size_t workspace_bytes, argus_stream_t stream) {
+  if (int e = pose_tail_check("pose_tail", batch, d, g0, w0, b0, w2, b2, w4, b4, pred, pose, workspace, workspace_bytes))
+    return e;
   unsigned* tk = reinterpret_cast<unsigned*>(workspace);
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kHeadTicketBytes);
-  hipLaunchKernelGGL(pose_tail_kernel, dim3(d / kHeadSlice), dim3(256), 0, (hipStream_t)stream, batch, d, g0, w0, b0, w2,
-                     b2, w4, b4, pred, pose, canonical_w, tk, part);
+  hipLaunchKernelGGL(pose_tail_kernel<false>, dim3(d / kHeadSlice), dim3(256), 0, (hipStream_t)stream, batch, d, g0, w0,
+                     b0, w2, b2, w4, b4, pred, pose, canonical_w, tk, part, RoiFrame{}, (const float*)nullptr,
+                     (const float*)nullptr);
   return check_launch("pose_tail_kernel");
+}
+
+int argus_pose_tail_roi(int batch, int d, const float* g0, const float* w0, const float* b0, const float* w2,
+                        const float* b2, const float* w4, const float* b4, float* pred, float* pose, int canonical_w,
+                        int n_cams, int frame_h, int frame_w, int h, int w, const float* rois, const float* w_r,
+                        void* workspace, size_t workspace_bytes, argus_stream_t stream) {
+  if (int e = pose_tail_check("pose_tail_roi", batch, d, g0, w0, b0, w2, b2, w4, b4, pred, pose, workspace,
+                              workspace_bytes))
+    return e;
+  auto refuse = [](const std::string& what) {
+    set_error("pose_tail_roi: " + what);
+    return ARGUS_ERR_ARG;
+  };
+  if (!rois) return refuse("rois is null");
+  if (!w_r) return refuse("w_r is null");
+  if (const char* why = roi_frame_refusal(n_cams, frame_h, frame_w, h, w)) return refuse(why);
+  if (batch * n_cams > kHeadRows)
+    return refuse("serves batch * n_cams 1..16 (the deployment path; larger batches use argus_roi_embed)");
+  unsigned* tk = reinterpret_cast<unsigned*>(workspace);
+  float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kHeadTicketBytes);
+  const RoiFrame F{n_cams, (float)frame_h, (float)frame_w, (float)h, (float)w};
+  hipLaunchKernelGGL(pose_tail_kernel<true>, dim3(d / kHeadSlice), dim3(256), 0, (hipStream_t)stream, batch, d, g0, w0,
+                     b0, w2, b2, w4, b4, pred, pose, canonical_w, tk, part, F, rois, w_r);
+  return check_launch("pose_tail_roi_kernel");
+}
+
+int argus_roi_embed(int batch, int n_cams, int frame_h, int frame_w, int h, int w, const float* rois,
+                    const float* w_r, float* z, float* g, float* rho, argus_stream_t stream) {
+  auto refuse = [](const std::string& what) {
+    set_error("roi_embed: " + what);
+    return ARGUS_ERR_ARG;
+  };
+  const char* null_arg = !rois ? "rois" : !w_r ? "w_r" : !z ? "z" : nullptr;
+  if (null_arg) return refuse(std::string(null_arg) + " is null");
+  if (batch <= 0) return refuse("batch must be positive");
+  if (const char* why = roi_frame_refusal(n_cams, frame_h, frame_w, h, w)) return refuse(why);
+  const RoiFrame F{n_cams, (float)frame_h, (float)frame_w, (float)h, (float)w};
+  hipLaunchKernelGGL(roi_embed_kernel, dim3((unsigned)batch), dim3(kEmbedCols), 0, (hipStream_t)stream, F, rois, w_r,
+                     z, g, rho);
+  return check_launch("roi_embed_kernel");
 }
 
 }  // extern "C"

@@ -72,9 +72,12 @@ class ResNetEngine:
     """Workspace + launch schedule for one (batch, H, W, dtype) configuration on one device."""
 
     def __init__(self, n_cams: int, resnet_output_dim: int, dtype: str, device: torch.device,
-                 tuning: dict | None = None):
+                 tuning: dict | None = None, roi_frame_hw: tuple | None = None):
         if dtype not in ("fp32", "bf16x3", "bf16", "fp8"):
             raise ValueError(f"compute dtype must be 'fp32', 'bf16x3', 'bf16' or 'fp8', got {dtype!r}")
+        # (Hs, Ws) of the frames the regions of interest are measured in: the head of a conditioned model
+        # (NCameraCNNConfig.roi_frame_hw) adds rho @ roi_embed.weight.T to output_mlp.0's pre-activation
+        self.roi_frame_hw = None if roi_frame_hw is None else (int(roi_frame_hw[0]), int(roi_frame_hw[1]))
         self.L = lib()
         # per-call overrides of the library's kernel-selection policy, attached to every conv descriptor
         # of this engine (argus_conv_desc.tuning; None = the library defaults, the benched selection)
@@ -368,6 +371,7 @@ class ResNetEngine:
         self.h0 = self._f(N, self.rdim)
         self.g0 = self._f(B, self.n_cams * self.rdim)
         self.h1, self.g1 = self._f(B, 128), self._f(B, 128)
+        self.rho = self._f(B, 4 * self.n_cams) if self.roi_frame_hw is not None else None  # region features
         self.h2, self.g2 = self._f(B, 128), self._f(B, 128)
         self.pred = self._f(B, 6)
         self.dh2, self.dh1 = self._f(B, 128), self._f(B, 128)
@@ -376,6 +380,8 @@ class ResNetEngine:
         D = self.n_cams * self.rdim
         shapes = [(N, self.rdim, Fd), (B, 128, D), (B, 128, 128), (B, 6, 128), (6, 128, B), (B, 128, 6),
                   (128, 128, B), (128, D, B), (B, D, 128), (self.rdim, Fd, N), (N, Fd, self.rdim)]
+        if self.roi_frame_hw is not None:
+            shapes.append((128, 4 * self.n_cams, B))
         hws = max(L.dll.argus_gemm_f32_workspace_bytes(*sh) for sh in shapes)
         self.gemm_ws = torch.empty(max(hws, 16), dtype=torch.uint8, device=self.device)
         self.gemm_ws_side = torch.empty(max(hws, 16), dtype=torch.uint8, device=self.device)
@@ -495,10 +501,15 @@ class ResNetEngine:
         self.L.conv_weight_prep_batch(self.cdt, self._wp_n, ptr(self._wp_table), self._wp_blocks, stream())
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: torch.Tensor, P: dict, Bf: dict, training: bool) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, P: dict, Bf: dict, training: bool,
+                roi: torch.Tensor | None = None) -> torch.Tensor:
+        """``roi``: the (B, n_cams, 4) fp32 regions of a conditioned model's images (``models.checked_roi``
+        validated them); no gradient flows to it."""
         B, Cn, H, W = x.shape
         if Cn != 3 * self.n_cams:
             raise ValueError(f"expected {3 * self.n_cams} input channels, got {Cn}")
+        if (roi is not None) != (self.roi_frame_hw is not None):
+            raise ValueError("roi: the regions go with an engine built with roi_frame_hw, and only with one")
         self.ensure(B, H, W)
         self._alloc_y3()
         x = x.contiguous()
@@ -578,7 +589,12 @@ class ResNetEngine:
         w0, b0 = P["output_mlp.0.weight"], P["output_mlp.0.bias"]
         w2, b2 = P["output_mlp.2.weight"], P["output_mlp.2.bias"]
         w4, b4 = P["output_mlp.4.weight"], P["output_mlp.4.bias"]
-        L.gemm_f32(B, 128, D, ptr(self.g0), D, 0, ptr(w0), D, 1, ptr(self.g1), 128, ptr(b0), 2, ptr(self.h1), ptr(self.gemm_ws), self.gemm_ws.numel(), s)
+        if roi is None:
+            L.gemm_f32(B, 128, D, ptr(self.g0), D, 0, ptr(w0), D, 1, ptr(self.g1), 128, ptr(b0), 2, ptr(self.h1), ptr(self.gemm_ws), self.gemm_ws.numel(), s)
+        else:  # h1 = output_mlp.0(g0) + rho @ roi_embed.weight.T (the full pre-activation), g1 = gelu(h1)
+            L.gemm_f32(B, 128, D, ptr(self.g0), D, 0, ptr(w0), D, 1, ptr(self.h1), 128, ptr(b0), 1, None, ptr(self.gemm_ws), self.gemm_ws.numel(), s)
+            L.roi_embed(B, self.n_cams, *self.roi_frame_hw, H, W, ptr(roi), ptr(P["roi_embed.weight"]), ptr(self.h1),
+                        ptr(self.g1), ptr(self.rho), s)
         L.gemm_f32(B, 128, 128, ptr(self.g1), 128, 0, ptr(w2), 128, 1, ptr(self.g2), 128, ptr(b2), 2, ptr(self.h2), ptr(self.gemm_ws), self.gemm_ws.numel(), s)
         L.gemm_f32(B, 6, 128, ptr(self.g2), 128, 0, ptr(w4), 128, 1, ptr(self.pred), 6, ptr(b4), 1, None, ptr(self.gemm_ws), self.gemm_ws.numel(), s)
         self.saved = training
@@ -632,6 +648,10 @@ class ResNetEngine:
             L.gemm_f32(128, D, B, ptr(self.dh1), 128, 1, ptr(self.g0), D, 0, ptr(G["output_mlp.0.weight"]), D, None, 0,
                        None, w2s, w2n, ss)
             L.colsum_f32(B, 128, ptr(self.dh1), 128, ptr(G["output_mlp.0.bias"]), ss)
+            if self.roi_frame_hw is not None:  # dh1 is the gradient of the full pre-activation: dh1^T rho
+                K = 4 * self.n_cams
+                L.gemm_f32(128, K, B, ptr(self.dh1), 128, 1, ptr(self.rho), K, 0, ptr(G["roi_embed.weight"]), K, None,
+                           0, None, w2s, w2n, ss)
             L.gemm_f32(R, 2048, N, ptr(self.dh0), R, 1, ptr(self.feat), 2048, 0, ptr(G["resnet.fc.weight"]), 2048, None, 0,
                        None, w2s, w2n, ss)
             L.colsum_f32(N, R, ptr(self.dh0), R, ptr(G["resnet.fc.bias"]), ss)

@@ -42,6 +42,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from argus_amd._lib import FOLD_ENTRY_BYTES, BnBwdPrologue, FoldSrc, ptr, stream
+from argus_amd.infer import _refuse_roi
 from argus_amd.infer_grad import SERVED, GradientSession
 from argus_amd.models import NCameraCNN
 from argus_amd.step import FlatParams
@@ -126,6 +127,7 @@ class FineTuneSession(GradientSession):
     def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
                  lr: float = 1e-4, max_grad_norm: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, trainable: str = "all", graph: bool = True, debug: bool = False):
+        _refuse_roi(model, type(self).__name__)
         dtype = model.compute_dtype if compute_dtype is None else compute_dtype
         if dtype not in SERVED:
             raise ValueError(f"FineTuneSession serves compute_dtype 'fp32' and 'bf16', got {dtype!r} (no fp16, fp8 "

@@ -55,14 +55,25 @@ def _require_cuda(model):
     return p0
 
 
+def _refuse_roi(model, who: str) -> None:
+    """Only PoseSession serves a model conditioned on the region of interest (NCameraCNNConfig.roi_frame_hw)."""
+    if getattr(model, "roi_frame_hw", None) is not None:
+        raise ValueError(f"{who} does not serve a model built with roi_frame_hw = {model.roi_frame_hw}: it has no "
+                         f"region-of-interest input (PoseSession(roi=True) does)")
+
+
 class InferenceSession:
     """``session(images) -> (batch, 6)`` for a fixed ``batch`` and image size ``hw``.
 
     ``compute_dtype``: "fp32", "bf16" or "fp16" (default: the model's; "fp16" only when asked for). ``graph``: capture the forward once per
     input dtype (fp32 / uint8) and replay it per call; False issues the same launches eagerly."""
 
+    _serves_roi = False  # a conditioned model (roi_frame_hw) is refused; PoseSession overrides
+
     def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
                  graph: bool = True):
+        if not self._serves_roi:
+            _refuse_roi(model, type(self).__name__)
         dtype = model.compute_dtype if compute_dtype is None else compute_dtype
         if dtype not in SERVED:
             raise ValueError(f"InferenceSession serves compute_dtype 'fp32' and 'bf16' (and 'fp16' when passed "
@@ -187,13 +198,16 @@ class InferenceSession:
                                 ptr(Bf[cv.bn + ".running_var"]), C.c_float(eps[cv.bn])), s)
             if self.compute_dtype == "fp16":
                 self._check_f16_range()
-            for n in ("resnet.fc", "output_mlp.0", "output_mlp.2", "output_mlp.4"):
-                for k in ("weight", "bias"):
-                    src = P[f"{n}.{k}"].detach()
-                    if (n, k) in self.head:
-                        self.head[n, k].copy_(src)  # in place: captured graphs keep reading these tensors
-                    else:
-                        self.head[n, k] = src.clone().contiguous()
+            names = [(n, k) for n in ("resnet.fc", "output_mlp.0", "output_mlp.2", "output_mlp.4")
+                     for k in ("weight", "bias")]
+            if "roi_embed.weight" in P:
+                names.append(("roi_embed", "weight"))
+            for n, k in names:
+                src = P[f"{n}.{k}"].detach()
+                if (n, k) in self.head:
+                    self.head[n, k].copy_(src)  # in place: captured graphs keep reading these tensors
+                else:
+                    self.head[n, k] = src.clone().contiguous()
         self.weight_bytes = (self.stem_wf.numel() * self.stem_wf.element_size() + 8 * 64
                              + sum(cv.wf.numel() * cv.wf.element_size() + 4 * cv.bias.numel()
                                    for cv in self.convs.values())
@@ -274,13 +288,18 @@ class InferenceSession:
         L.gemm_f32(N, R, 2048, ptr(self.feat), 2048, 0, ptr(hd["resnet.fc", "weight"]), 2048, 1, ptr(self.h0), R,
                    ptr(hd["resnet.fc", "bias"]), 1, None, ws, wsn, s)
         L.gelu_f32(B * D, ptr(self.h0), ptr(self.g0), s)
-        L.gemm_f32(B, 128, D, ptr(self.g0), D, 0, ptr(hd["output_mlp.0", "weight"]), D, 1, ptr(self.g1), 128,
-                   ptr(hd["output_mlp.0", "bias"]), 2, ptr(self.h1), ws, wsn, s)
+        self._mlp0(ws, wsn, s)
         L.gemm_f32(B, 128, 128, ptr(self.g1), 128, 0, ptr(hd["output_mlp.2", "weight"]), 128, 1, ptr(self.g2), 128,
                    ptr(hd["output_mlp.2", "bias"]), 2, ptr(self.h2), ws, wsn, s)
         L.gemm_f32(B, 6, 128, ptr(self.g2), 128, 0, ptr(hd["output_mlp.4", "weight"]), 128, 1, ptr(self.pred), 6,
                    ptr(hd["output_mlp.4", "bias"]), 1, None, ws, wsn, s)
         return self.pred
+
+    def _mlp0(self, ws, wsn, s) -> None:
+        """g1 = gelu(h1), h1 = output_mlp.0(g0): one GEMM with the bias + GELU epilogue."""
+        L, B, D, hd = self.L, self.batch, self.n_cams * self.rdim, self.head
+        L.gemm_f32(B, 128, D, ptr(self.g0), D, 0, ptr(hd["output_mlp.0", "weight"]), D, 1, ptr(self.g1), 128,
+                   ptr(hd["output_mlp.0", "bias"]), 2, ptr(self.h1), ws, wsn, s)
 
     def _check_images(self, images, who: str) -> None:
         want = (self.batch, 3 * self.n_cams, *self.hw)

@@ -33,7 +33,7 @@ import ctypes as C
 import torch
 
 from argus_amd._lib import BnBwdPrologue, ptr, stream
-from argus_amd.infer import InferenceSession
+from argus_amd.infer import InferenceSession, _refuse_roi
 from argus_amd.models import NCameraCNN
 
 SERVED = ("fp32", "bf16")
@@ -47,6 +47,7 @@ class GradientSession(InferenceSession):
 
     def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
                  graph: bool = True, debug: bool = False):
+        _refuse_roi(model, type(self).__name__)
         dtype = model.compute_dtype if compute_dtype is None else compute_dtype
         if dtype not in SERVED:
             raise ValueError(f"GradientSession serves compute_dtype 'fp32' and 'bf16', got {dtype!r} (no fp16, fp8 "

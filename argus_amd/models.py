@@ -42,6 +42,9 @@ class NCameraCNNConfig:
 
     n_cams: int = 2
     resnet_output_dim: int = 1024
+    # Extension: (Hs, Ws) of the frames whose regions of interest the images are resampled from. None is the
+    # reference's model; a size adds ``roi_embed`` (see NCameraCNN) and makes ``forward`` take the regions.
+    roi_frame_hw: Optional[tuple] = None
 
 
 # ---- parameter containers in torchvision's order (RNG consumption = models.resnet50()) ----------
@@ -82,13 +85,13 @@ class _NetFn(torch.autograd.Function):
     """Whole-network Function: forward/backward are the native HIP schedule (argus_amd.engine)."""
 
     @staticmethod
-    def forward(ctx, x, model, *params):
+    def forward(ctx, x, model, roi, *params):
         if ctx.needs_input_grad[0] and x.dtype != torch.float32:
             raise RuntimeError(f"argus_amd: the image gradient is produced for fp32 images only, got {x.dtype} "
                                "images that require grad (convert them with .float() first)")
         engine = model._engine(x.device)
         P, Bf = model._maps()
-        pred = engine.forward(x, P, Bf, model.training).clone()
+        pred = engine.forward(x, P, Bf, model.training, roi=roi).clone()  # roi: carried through, no gradient
         engine.fwd_id = getattr(engine, "fwd_id", 0) + 1
         ctx.engine, ctx.model, ctx.fwd_id = engine, model, engine.fwd_id
         ctx.x_shape = tuple(x.shape)
@@ -117,7 +120,7 @@ class _NetFn(torch.autograd.Function):
         for name, p in model.named_parameters():
             g = G[name]
             grads.append(g.permute(0, 3, 1, 2) if g.dim() == 4 else g)
-        return (dx, None, *grads)
+        return (dx, None, None, *grads)
 
 
 def strip_checkpoint_prefixes(state_dict):
@@ -138,8 +141,52 @@ def strip_checkpoint_prefixes(state_dict):
     return out
 
 
+ROI_MAX_CAMS = 16  # argus_roi_embed / argus_pose_tail_roi serve 4 * n_cams <= 64 region features
+
+
+def roi_features(roi: torch.Tensor, frame_hw: tuple, hw: tuple) -> torch.Tensor:
+    """The definition of the region features, in the dtype of ``roi`` (documentation and host-side checks; the
+    product computes them in argus_roi_embed / argus_pose_tail_roi). ``roi`` (..., 4) = (y0, x0, eh, ew) in pixels
+    of a ``frame_hw`` frame, resampled to ``hw``: centre offset over the frame size per axis, then ln(extent /
+    output length) per axis."""
+    (Hs, Ws), (h, w) = frame_hw, hw
+    y0, x0, eh, ew = roi.unbind(-1)
+    return torch.stack([(y0 + eh / 2 - Hs / 2) / Hs, (x0 + ew / 2 - Ws / 2) / Ws, torch.log(eh / h),
+                        torch.log(ew / w)], dim=-1)
+
+
+def crop_roi(batch: int, n_cams: int, origin: tuple, hw: tuple, device) -> torch.Tensor:
+    """The (batch, n_cams, 4) fp32 regions of images that are the crop at ``origin`` of size ``hw`` (unit scale)."""
+    return torch.tensor([*origin, *hw], dtype=torch.float32, device=device).expand(batch, n_cams, 4).contiguous()
+
+
+def checked_roi(model, images: torch.Tensor, roi, who: str):
+    """The ``roi`` argument of ``who`` against ``model``: None for a plain model, the contiguous (B, n_cams, 4)
+    fp32 tensor on the images' device for a conditioned one. ValueError otherwise, before any device work."""
+    if model.roi_frame_hw is None:
+        if roi is not None:
+            raise ValueError(f"{who}: roi given to a model built without roi_frame_hw (NCameraCNNConfig)")
+        return None
+    if roi is None:
+        raise ValueError(f"{who}: this model is conditioned on the region of interest (roi_frame_hw = "
+                         f"{model.roi_frame_hw}): pass roi, the (B, n_cams, 4) regions (y0, x0, height, width)")
+    want = (images.shape[0], model.n_cams, 4)
+    if not isinstance(roi, torch.Tensor) or tuple(roi.shape) != want or roi.dtype != torch.float32:
+        raise ValueError(f"{who}: roi must be a float32 tensor of shape {want}, got "
+                         f"{(tuple(roi.shape), roi.dtype) if isinstance(roi, torch.Tensor) else type(roi).__name__}")
+    if roi.device != images.device:
+        raise ValueError(f"{who}: roi is on {roi.device}, the images on {images.device}")
+    return roi.detach().contiguous()
+
+
 class NCameraCNN(nn.Module):
-    """A CNN which assumes N cameras are available in the scene (argus/models.py:26-90)."""
+    """A CNN which assumes N cameras are available in the scene (argus/models.py:26-90).
+
+    Extension: ``NCameraCNNConfig(roi_frame_hw=(Hs, Ws))`` conditions the head on the region of interest each
+    camera image was resampled from (``PoseSession(roi=True)``, ``ResidentLoader(roi_jitter / roi_track)``): one
+    more parameter, ``roi_embed.weight`` (128, 4 * n_cams), registered last and initialised to zero, acts on
+    ``output_mlp.0``'s pre-activation: ``z1 = output_mlp.0(g0) + roi_features(roi) @ roi_embed.weight.T``. At
+    zero it is the unconditioned function, so a plain checkpoint (``load_state_dict`` accepts one) is its start."""
 
     def __init__(self, cfg: Optional[NCameraCNNConfig] = None, compute_dtype: str = "fp32",
                  kernel_tuning: Optional[dict] = None) -> None:
@@ -158,6 +205,18 @@ class NCameraCNN(nn.Module):
             nn.GELU(),
             nn.Linear(128, 6),
         )
+        self.roi_frame_hw = None
+        if cfg.roi_frame_hw is not None:
+            if len(tuple(cfg.roi_frame_hw)) != 2 or min(int(v) for v in cfg.roi_frame_hw) <= 0:
+                raise ValueError(f"NCameraCNNConfig roi_frame_hw: expected (Hs, Ws) > 0, got {cfg.roi_frame_hw!r}")
+            if self.n_cams > ROI_MAX_CAMS:
+                raise ValueError(f"NCameraCNNConfig roi_frame_hw: serves n_cams <= {ROI_MAX_CAMS}, got {self.n_cams}")
+            self.roi_frame_hw = (int(cfg.roi_frame_hw[0]), int(cfg.roi_frame_hw[1]))
+            # registered after output_mlp: every other parameter keeps its flat offset (step.FlatParams) and the
+            # head's gradient bucket ("resnet.fc.weight" and everything after it) covers the new slot. Built
+            # without touching the generator, then zeroed: seeded initialisation equals the plain model's.
+            self.roi_embed = nn.utils.skip_init(nn.Linear, 4 * self.n_cams, 128, bias=False)
+            nn.init.zeros_(self.roi_embed.weight)
         self.compute_dtype = compute_dtype
         # optional kernel-selection overrides ({policy key: value}, argus_conv_policy_default) for this
         # model's engines - experiments and the kernel-coverage tests; None = the library defaults
@@ -173,7 +232,8 @@ class NCameraCNN(nn.Module):
         key = (str(device), self.compute_dtype, tuning)
         eng = self._engines.get(key)
         if eng is None:
-            eng = ResNetEngine(self.n_cams, self.resnet_output_dim, self.compute_dtype, device, dict(tuning))
+            eng = ResNetEngine(self.n_cams, self.resnet_output_dim, self.compute_dtype, device, dict(tuning),
+                               roi_frame_hw=self.roi_frame_hw)
             self._engines[key] = eng
         return eng
 
@@ -219,19 +279,29 @@ class NCameraCNN(nn.Module):
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         """``nn.Module.load_state_dict`` that also takes the reference's wrapped checkpoints: keys
         prefixed ``module.`` (a DDP model's state_dict, argus/train.py:199,358) or ``_orig_mod.``
-        (a ``torch.compile``d model, train.py:61) are stripped first."""
-        return super().load_state_dict(strip_checkpoint_prefixes(state_dict), strict=strict, assign=assign)
+        (a ``torch.compile``d model, train.py:61) are stripped first.
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """(B, 3*n_cams, H, W) fp32 images in [0, 1] -> (B, 6) se(3) poses.
+        A conditioned model (``roi_frame_hw``) takes a state dict without ``roi_embed.weight``, the checkpoint of
+        an unconditioned model, and sets that weight to zero: it then computes what the checkpoint's model does.
+        Every other mismatch behaves as ``nn.Module.load_state_dict``'s."""
+        state_dict = strip_checkpoint_prefixes(state_dict)
+        if self.roi_frame_hw is not None and "roi_embed.weight" not in state_dict:
+            state_dict["roi_embed.weight"] = torch.zeros_like(self.roi_embed.weight)
+        return super().load_state_dict(state_dict, strict=strict, assign=assign)
+
+    def forward(self, x: torch.Tensor, roi: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(B, 3*n_cams, H, W) fp32 images in [0, 1] -> (B, 6) se(3) poses. ``roi``: the (B, n_cams, 4) fp32
+        regions (y0, x0, height, width) the images were resampled from, on their device: required by a model
+        built with ``roi_frame_hw``, refused (ValueError) by any other. No gradient flows to it.
 
         Extension: uint8 images in [0, 255] (``CameraCubePoseDataset(uint8=True)``) are accepted too;
         the reference's ``/ 255.0`` (argus/data.py:214-215) then runs on the device, bit-identically."""
         assert len(x.shape) == 4, "The input images must be of shape (B, C, H, W)! If B=1, add a dummy dimension."
+        roi = checked_roi(self, x, roi, "NCameraCNN.forward")
         if x.device.type != "cuda":
             raise RuntimeError("argus_amd.NCameraCNN runs only on the MI355X HIP path: move the model and the "
                                "images to a cuda device (there is no CPU fallback)")
         params = [p for _, p in self.named_parameters()]
         if any(p.device != x.device or p.dtype != torch.float32 for p in params):
             raise RuntimeError("argus_amd.NCameraCNN parameters must be fp32 on the input's device")
-        return _NetFn.apply(x, self, *params)
+        return _NetFn.apply(x, self, roi, *params)

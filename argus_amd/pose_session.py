@@ -90,6 +90,15 @@ class PoseSession(InferenceSession):
     def __init__(self, model: NCameraCNN, batch: int, hw: tuple, compute_dtype: str | None = None,
                  graph: bool = True, frame_hw: tuple | None = None, layout: str = "chw", fused_stem: bool = True,
                  fused_head: bool = True, roi: bool = False, track: TrackConfig | None = None):
+        self.roi_frame_hw = getattr(model, "roi_frame_hw", None)
+        if self.roi_frame_hw is not None:  # a model conditioned on the region each camera saw
+            if not roi and track is None:
+                raise ValueError(f"PoseSession: the model is built with roi_frame_hw = {self.roi_frame_hw}, its head "
+                                 f"reads the region of interest: pass roi=True (or track=)")
+            fhw = tuple(int(v) for v in (hw if frame_hw is None else frame_hw))
+            if fhw != self.roi_frame_hw:
+                raise ValueError(f"PoseSession: frame_hw {fhw} is not the model's roi_frame_hw {self.roi_frame_hw}: "
+                                 f"the region features are measured in that frame")
         if track is not None:
             if not isinstance(track, TrackConfig):
                 raise ValueError(f"PoseSession track: expected a TrackConfig, got {type(track).__name__}")
@@ -123,9 +132,13 @@ class PoseSession(InferenceSession):
         super().__init__(model, batch, hw, dtype, graph)
 
     # ------------------------------------------------------------------ construction
+    _serves_roi = True
+
     def _plan(self) -> None:
         super()._plan()
         self.launches_per_forward = (1 if self.fused_stem else 3) + len(self.convs) + (2 if self.fused_head else 6)
+        if self.roi_frame_hw is not None and not self.fused_head:
+            self.launches_per_forward += 1  # argus_roi_embed behind output_mlp.0's GEMM
         if self.track is not None:
             self.launches_per_forward += 1  # argus_roi_from_pose behind argus_pose_tail
 
@@ -251,6 +264,18 @@ class PoseSession(InferenceSession):
             h = out
         return self._head(h)
 
+    def _mlp0(self, ws, wsn, s) -> None:
+        """``fused_head=False``: output_mlp.0 of a conditioned model is the GEMM with the bias epilogue, then
+        argus_roi_embed on the regions the stem read in this forward (the second implementation the fused tail is
+        compared with)."""
+        if self.roi_frame_hw is None:
+            return super()._mlp0(ws, wsn, s)
+        L, B, D, hd = self.L, self.batch, self.n_cams * self.rdim, self.head
+        L.gemm_f32(B, 128, D, ptr(self.g0), D, 0, ptr(hd["output_mlp.0", "weight"]), D, 1, ptr(self.h1), 128,
+                   ptr(hd["output_mlp.0", "bias"]), 1, None, ws, wsn, s)
+        L.roi_embed(B, self.n_cams, *self.frame_hw, *self.hw, ptr(self._roi), ptr(hd["roi_embed", "weight"]),
+                    ptr(self.h1), ptr(self.g1), None, s)
+
     def _head(self, h: torch.Tensor) -> torch.Tensor:
         if not self.fused_head:
             return super()._head(h)
@@ -259,10 +284,14 @@ class PoseSession(InferenceSession):
         hd, D = self.head, self.n_cams * self.rdim
         L.pool_fc_gelu(self.dt, N, hf * wf, 2048, ptr(h), ptr(hd["resnet.fc", "weight"]), ptr(hd["resnet.fc", "bias"]),
                        self.rdim, ptr(self.g0), ptr(self.fc_ws), self.fc_ws.numel(), s)
-        L.pose_tail(B, D, ptr(self.g0), ptr(hd["output_mlp.0", "weight"]), ptr(hd["output_mlp.0", "bias"]),
-                    ptr(hd["output_mlp.2", "weight"]), ptr(hd["output_mlp.2", "bias"]),
-                    ptr(hd["output_mlp.4", "weight"]), ptr(hd["output_mlp.4", "bias"]), ptr(self.pred),
-                    ptr(self.pose_out), 0, ptr(self.tail_ws), self.tail_ws.numel(), s)
+        mlp = (ptr(hd["output_mlp.0", "weight"]), ptr(hd["output_mlp.0", "bias"]),
+               ptr(hd["output_mlp.2", "weight"]), ptr(hd["output_mlp.2", "bias"]),
+               ptr(hd["output_mlp.4", "weight"]), ptr(hd["output_mlp.4", "bias"]), ptr(self.pred), ptr(self.pose_out), 0)
+        if self.roi_frame_hw is None:
+            L.pose_tail(B, D, ptr(self.g0), *mlp, ptr(self.tail_ws), self.tail_ws.numel(), s)
+        else:  # self._roi: the regions the stem read in this forward; argus_roi_from_pose overwrites them BEHIND this
+            L.pose_tail_roi(B, D, ptr(self.g0), *mlp, self.n_cams, *self.frame_hw, *self.hw, ptr(self._roi),
+                            ptr(hd["roi_embed", "weight"]), ptr(self.tail_ws), self.tail_ws.numel(), s)
         if self.track is not None:  # the region the NEXT forward reads, in place: the tracker's only step
             L.roi_from_pose(B, self.n_cams, *self.frame_hw, *self.hw, ptr(self.pose_out), B, None, ptr(self._cameras),
                             C.byref(self._track_cfg), None, ptr(self._home), ptr(self._roi), ptr(self._roi_used),

@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from argus_amd._lib import lib, ptr, stream
+from argus_amd.models import checked_roi
 
 
 class FlatParams:
@@ -143,7 +144,24 @@ class FusedTrainer:
         ``image_grad`` (optional): a contiguous fp32 tensor of the images' shape on their device; d(mean
         loss)/d(images) of this step is written into it by the same backward that feeds Adam (the "free"
         adversarial-training pattern). Under data parallelism it is this rank's gradient of its local mean
-        loss: nothing is all-reduced."""
+        loss: nothing is all-reduced.
+
+        A model built with ``roi_frame_hw`` is refused (ValueError): its step is ``step_roi``."""
+        if getattr(self.model, "roi_frame_hw", None) is not None:
+            raise ValueError(f"FusedTrainer.step: this model is conditioned on the region of interest (roi_frame_hw = "
+                             f"{self.model.roi_frame_hw}): pass roi through step_roi(images, targets, roi)")
+        return self._step(images, targets, image_grad, None)
+
+    def step_roi(self, images: torch.Tensor, targets: torch.Tensor, roi: torch.Tensor,
+                 image_grad: torch.Tensor | None = None) -> torch.Tensor:
+        """``step`` for a model built with ``roi_frame_hw``. ``roi``: the (B, n_cams, 4) fp32 regions the images
+        were resampled from (``ResidentLoader``'s ``batch["roi"]``) on their device, validated as
+        ``NCameraCNN.forward`` validates them; a model built without ``roi_frame_hw`` is refused (ValueError).
+        ``roi_embed.weight`` is trained with every other parameter; no gradient flows to the regions."""
+        roi = checked_roi(self.model, images, roi, "FusedTrainer.step_roi")
+        return self._step(images, targets, image_grad, roi)
+
+    def _step(self, images, targets, image_grad, roi) -> torch.Tensor:
         model = self.model
         if not model.training:
             raise RuntimeError("FusedTrainer.step needs model.train()")
@@ -156,7 +174,7 @@ class FusedTrainer:
         eng = model._engine(images.device)
         P, Bf = model._maps()
         targets = targets.contiguous().float()
-        pred = eng.forward(images, P, Bf, True)
+        pred = eng.forward(images, P, Bf, True, roi=roi)
         if self._loss is None or self._loss.shape[0] != B:
             self._loss = torch.empty(B, dtype=torch.float32, device=images.device)
             self._dpred = torch.empty(B, 6, dtype=torch.float32, device=images.device)

@@ -51,7 +51,7 @@ from torch.utils.data.distributed import DistributedSampler
 from argus_amd import ROOT
 from argus_amd.data import AugmentationConfig, CameraCubePoseDataset, CameraCubePoseDatasetConfig
 from argus_amd.losses import geometric_loss_fn
-from argus_amd.models import NCameraCNN, NCameraCNNConfig
+from argus_amd.models import NCameraCNN, NCameraCNNConfig, crop_roi
 
 __all__ = ["TrainConfig", "geometric_loss_fn", "initialize_training", "train", "PlateauScheduler", "main",
            "sync_bn_buffers"]
@@ -59,6 +59,12 @@ __all__ = ["TrainConfig", "geometric_loss_fn", "initialize_training", "train", "
 
 def _gpu_count() -> int:
     return torch.cuda.device_count()
+
+
+ROI_FEATURES_NEEDS = ("--roi-features needs --resident-dataset and one of --roi-jitter / --roi-track: the regions the "
+                      "head is told about are the resident loader's")
+ROI_FEATURES_FREEZE_BN = ("--roi-features is not served with --freeze-bn: FineTuneSession does not take a model built "
+                          "with roi_frame_hw")
 
 
 @dataclass(frozen=True)
@@ -112,10 +118,21 @@ class TrainConfig:
     # labelled cube by argus_roi_from_pose from the calibration file (track.load_calibration), the arithmetic a
     # PoseSession(track=...) deploys; --roi-jitter then jitters around the cube. Validation keeps the center crop.
     roi_track: Optional[str] = None
+    # extension (--roi-features, with --resident-dataset and --roi-jitter or --roi-track): condition the head on the
+    # region each camera image was resampled from: the model is built with roi_frame_hw = the frames' size (one more
+    # parameter, roi_embed.weight, zero at the start) and is given the batch's regions; validation passes the center
+    # crop's region. An --init-checkpoint of an unconditioned model loads (the weight starts at zero).
+    roi_features: bool = False
 
     def __post_init__(self) -> None:
         assert isinstance(self.save_dir, str)
         from argus_amd.finetune import TRAINABLE
+
+        if self.roi_features:
+            if not self.resident_dataset or (self.roi_jitter is None and self.roi_track is None):
+                raise ValueError(ROI_FEATURES_NEEDS)
+            if self.freeze_bn:
+                raise ValueError(ROI_FEATURES_FREEZE_BN)
 
         if self.roi_track is not None and not self.resident_dataset:
             raise ValueError("--roi-track needs --resident-dataset: the regions are computed and resampled by the "
@@ -280,7 +297,10 @@ def initialize_training(cfg: TrainConfig, rank: int = 0, world: int = 1):
     distributed = world > 1
 
     fp32_mode = "bf16x3" if cfg.float32_matmul_precision == "high" else "fp32"
-    model = NCameraCNN(cfg.model_config, compute_dtype="bf16" if cfg.amp else fp32_mode).to(device)
+    model_config = cfg.model_config
+    if cfg.roi_features:  # the regions are measured in the train split's uncropped frames
+        model_config = dataclasses.replace(model_config, roi_frame_hw=tuple(train_loader.ds.src_hw))
+    model = NCameraCNN(model_config, compute_dtype="bf16" if cfg.amp else fp32_mode).to(device)
     if cfg.init_checkpoint is not None:
         from argus_amd.models import strip_checkpoint_prefixes
 
@@ -336,7 +356,10 @@ def train(cfg: TrainConfig, rank: int = 0) -> str:
         for example in train_loader:
             images = trainer.augment(example["images"].to(device, non_blocking=True))
             target = example["cube_pose"].to(device, non_blocking=True)
-            losses = trainer.step(images, target)
+            if cfg.roi_features:
+                losses = trainer.step_roi(images, target, example["roi"])
+            else:
+                losses = trainer.step(images, target)
             epoch_losses.append(losses.clone())
             if wandb is not None:
                 wandb.log({"loss": losses.mean().item()})
@@ -348,7 +371,13 @@ def train(cfg: TrainConfig, rank: int = 0) -> str:
             tot = torch.zeros(2, dtype=torch.float64, device=device)
             with torch.no_grad():
                 for example in val_loader:
-                    pred = model(example["images"].to(device, non_blocking=True))
+                    images = example["images"].to(device, non_blocking=True)
+                    if cfg.roi_features:  # validation keeps the center crop: that crop's region for every image
+                        ds = val_loader.ds
+                        pred = model(images, roi=crop_roi(images.shape[0], ds.n_cams, ds.crop_origin, ds.crop_hw,
+                                                          device))
+                    else:
+                        pred = model(images)
                     vl = geometric_loss_fn(pred, example["cube_pose"].to(device, non_blocking=True))
                     tot += torch.stack([vl.double().sum(), torch.tensor(float(vl.numel()), device=device,
                                                                          dtype=torch.float64)])
@@ -440,6 +469,11 @@ def parse_args(argv=None) -> TrainConfig:
     if ns.get("roi_track") is not None and not ns.get("resident_dataset"):
         ap.error("--roi-track needs --resident-dataset: the regions are computed and resampled by the resident "
                  "loader's launches")
+    if ns.get("roi_features"):
+        if not ns.get("resident_dataset") or (ns.get("roi_jitter") is None and ns.get("roi_track") is None):
+            ap.error(ROI_FEATURES_NEEDS)
+        if ns.get("freeze_bn"):
+            ap.error(ROI_FEATURES_FREEZE_BN)
     if ns.get("float32_matmul_precision") not in (None, "highest", "high"):
         ap.error("--float32-matmul-precision must be 'highest' or 'high'")
     from argus_amd.finetune import TRAINABLE

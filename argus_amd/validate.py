@@ -14,6 +14,10 @@ out of scope) and the kornia photometric augmentations (the reference applies th
 ``use_train``; argus_amd.data warns about them). Batching (``batch_size`` > 1) gives the same
 per-example losses, since eval-mode BN is per-sample.
 
+A ``model_config`` with ``roi_frame_hw`` (a model conditioned on the region of interest, argus_amd.models) is given
+the region of the dataset's center crop in a frame of that size for every image; ``session_dtype`` then raises
+``ValueError`` (``InferenceSession`` does not serve conditioned models).
+
 ``session_dtype`` (``--session-dtype fp32|bf16|fp16``, an extension): the predictions come from an
 ``argus_amd.infer.InferenceSession`` of that compute dtype instead of ``model.eval()``, so a checkpoint's
 validation loss can be read at the precision it will be deployed in. A session has a fixed batch: the last
@@ -28,9 +32,10 @@ from typing import Optional
 import torch
 from torch.utils.data import DataLoader
 
-from argus_amd.data import AugmentationConfig, CameraCubePoseDataset, CameraCubePoseDatasetConfig
+from argus_amd.data import (AugmentationConfig, CameraCubePoseDataset, CameraCubePoseDatasetConfig,
+                            center_crop_slices)
 from argus_amd.losses import geometric_loss_fn
-from argus_amd.models import NCameraCNN, NCameraCNNConfig
+from argus_amd.models import NCameraCNN, NCameraCNNConfig, crop_roi
 
 
 def _default_device() -> str:
@@ -70,6 +75,10 @@ def load_model(model_path: str, model_config: NCameraCNNConfig | None = None, de
 
 def validate(cfg: ValConfig) -> list[float]:
     """Per-example validation losses of the checkpoint on the chosen split (validate.py:100-128)."""
+    frame_hw = cfg.model_config.roi_frame_hw
+    if frame_hw is not None and cfg.session_dtype is not None:
+        raise ValueError("validate: session_dtype is not served for a model_config with roi_frame_hw: "
+                         "InferenceSession does not serve conditioned models")
     model = load_model(cfg.model_path, cfg.model_config, cfg.device)
     dataset = CameraCubePoseDataset(cfg.dataset_config, cfg_aug=cfg.aug_config, train=cfg.use_train, uint8=True)
     loader = DataLoader(dataset, batch_size=cfg.batch_size, shuffle=False)
@@ -79,7 +88,11 @@ def validate(cfg: ValConfig) -> list[float]:
         for example in loader:
             images = example["images"].to(cfg.device)
             target = example["cube_pose"].to(cfg.device).to(torch.float32)
-            if cfg.session_dtype is None:
+            if frame_hw is not None:  # a conditioned model: the dataset's center crop is the region of every image
+                hw = tuple(images.shape[-2:])
+                ys, xs = center_crop_slices(frame_hw, hw)
+                pred = model(images, roi=crop_roi(images.shape[0], model.n_cams, (ys.start, xs.start), hw, cfg.device))
+            elif cfg.session_dtype is None:
                 pred = model(images)
             else:
                 if session is None:  # the first batch is a full one and fixes the session's shape

@@ -732,6 +732,36 @@ int argus_pose_tail(int batch, int d, const float* g0, const float* w0, const fl
                     const float* b2, const float* w4, const float* b4, float* pred, float* pose, int canonical_w,
                     void* workspace, size_t workspace_bytes, argus_stream_t stream);
 
+/* Region-of-interest conditioning of the pose head (argus_roi_embed, argus_pose_tail_roi: added at ABI 21
+ * without a version change: detect by symbol; csrc/head.hip). Image i = b * n_cams + c was resampled from the
+ * region rois[i] = (y0, x0, eh, ew) of a frame_h x frame_w frame to the network's h x w; its features are
+ *   rho[b][4c + 0] = (y0 + eh / 2 - frame_h / 2) / frame_h     rho[b][4c + 2] = ln(eh / h)
+ *   rho[b][4c + 1] = (x0 + ew / 2 - frame_w / 2) / frame_w     rho[b][4c + 3] = ln(ew / w)
+ * and output_mlp.0's pre-activation gains e[b][j] = sum_k w_r[j][k] * rho[b][k] (w_r (128, 4 n_cams) fp32, the
+ * parameter roi_embed.weight): e is accumulated from 0 with fmaf over k = 0 .. 4 n_cams - 1 in ascending order,
+ * fp32, logf for the logarithms. One device function states a feature and one states e for both entry points:
+ * they produce the same bits from the same region. Inside the domain argus_stem_infer_roi serves the first two
+ * features lie in [-1/2, 1/2] and the last two in [-ln 4, ln 4]. For ANY bits in rois the kernels only compute
+ * numbers from them (nothing is indexed by a region's value): a non-finite region gives a non-finite result.
+ * No atomics, bit-reproducible; nothing allocates or synchronises; capturable.
+ *
+ * argus_roi_embed (training and eval, any batch): z (batch, 128) holds output_mlp.0's acc + bias on entry
+ * (argus_gemm_f32 epilogue 1) and z + e on return; g (batch, 128, may be NULL) receives gelu(z); rho (batch,
+ * 4 n_cams, may be NULL) receives the features, the operand of the weight gradient dz^T rho. Refused before the
+ * launch (ARGUS_ERR_ARG, the message names the argument): null rois, w_r or z; batch, n_cams, frame_h or frame_w
+ * <= 0; h or w < 8; h > frame_h or w > frame_w; n_cams > 16.
+ *
+ * argus_pose_tail_roi: argus_pose_tail whose last arriver forms the pre-activation (slice sum + b0[j]) + e. The
+ * features and w_r are staged before the ticket, so the last arriver waits for no further memory round trip. With
+ * w_r = 0 pred and pose equal argus_pose_tail's bit for bit. Serves batch * n_cams <= 16 (more: ARGUS_ERR_ARG);
+ * otherwise refuses what argus_pose_tail and argus_roi_embed refuse. Workspace: argus_pose_tail_workspace_bytes. */
+int argus_roi_embed(int batch, int n_cams, int frame_h, int frame_w, int h, int w, const float* rois,
+                    const float* w_r, float* z, float* g, float* rho, argus_stream_t stream);
+int argus_pose_tail_roi(int batch, int d, const float* g0, const float* w0, const float* b0, const float* w2,
+                        const float* b2, const float* w4, const float* b4, float* pred, float* pose, int canonical_w,
+                        int n_cams, int frame_h, int frame_w, int h, int w, const float* rois, const float* w_r,
+                        void* workspace, size_t workspace_bytes, argus_stream_t stream);
+
 /* argus_roi_from_pose (added at ABI 21 without a version change: detect by symbol; csrc/track.hip): the region
  * of interest of every camera image around the cube a pose places in front of the cameras, in place on the
  * buffer argus_stem_infer_roi / argus_frames_resample / argus_batch_gather_resample read. Issued after
